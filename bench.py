@@ -2,8 +2,13 @@
 """bench.py - headline benchmark: 4K frames/s of videoconvertscale's NV12->BGRA path per GPU (BASELINE C2),
 plus the other BASELINE configs behind --config.
 
-  python bench.py [--config c2|c3|c4|c4audio|c5] [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--config c2|c3|c4|c4audio|c5] [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
+
+A plain run measures the headline only: setup, pre-heat, W warm-up steps, K timed steps, one JSON line.  `--full` adds what
+is measured beside it: C2's secondary section (one frame per launch, the element, the round-6 transcoding pairs) and the
+reference's CPU baseline.  `--dump-outputs DIR` writes what the last timed step computed (a fixed sample of it) as
+DIR/<name>.npy, so that two builds can be compared output for output on identical inputs.
 
 `--gpus N` without a torchrun environment re-executes itself under torch.distributed.run with N ranks
 (127.0.0.1 rendezvous); a rank count that differs from --gpus is an error, never a silent 1-GPU run.
@@ -147,6 +152,11 @@ class VideoWorkload:
                 self.conv.frames([self.in_ptrs[(n + i) % self.pool_in] for i in range(B)],
                                  [self.out_ptrs[(n + i) % self.pool_out] for i in range(B)], self.stream)
 
+    def outputs(self, s):
+        """The destination frames step s wrote (every frame of a step has a buffer of its own)."""
+        pout = self.keep[1]
+        return [("%s_frames" % self.ofmt.lower(), [pout[(s * self.frames_per_step + f) % self.pool_out] for f in range(self.frames_per_step)])]
+
     def config(self, world):
         return {"workload": "%s, %d frames/step, pools %d in / %d out resident in HBM, 1 stream per GPU, %d frame(s) per kernel launch"
                             % (CONFIG_TEXT[self.name], self.frames_per_step, self.pool_in, self.pool_out, self.batch),
@@ -229,6 +239,10 @@ class CompositorWorkload:
             r = self.L.gstamd_compositor_aggregate(self.V.FORMATS["BGRA"], 0, self.arrs[k % self.SETS], self.N,
                                                    self.outs[k % self.pool_out].data_ptr(), self.DW, self.DH, self.DW * 4, self.stream)
             assert r == 0, self.V.last_error()
+
+    def outputs(self, s):
+        """The canvases step s composited (c4opaque and c4a step the same way)."""
+        return [("bgra_canvases", [self.outs[(s * self.frames_per_step + f) % self.pool_out] for f in range(self.frames_per_step)])]
 
     def config(self, world):
         return {"workload": "%s, %d output frames/step, %d pad frames / %d canvases resident in HBM" %
@@ -429,6 +443,11 @@ class AudioWorkload:
             m = self.r.get_out_frames(n)
             self.r.resample(self.sig.data_ptr() + o * fsz, n, self.out.data_ptr() + po * fsz, m, self.stream)
             po += m
+        self.out_frames = po
+
+    def outputs(self, s):
+        """The resampled frames of the last step (a step is 3000 x 160 input frames: the resampler's phase is the same at every step's start)."""
+        return [("resampled", [self.out[:self.out_frames]])]
 
     def config(self, world):
         return {"workload": "%s, a step = 10 s of audio in buffers of %d frames (%d launches)" % (CONFIG_TEXT["c4audio"], self.block,
@@ -488,6 +507,7 @@ class AudioManyWorkload(AudioWorkload):
             self.calls.append(A.ManyBuffers(self.rs, [x.data_ptr() + o * fsz for x in self.sigs], [n] * self.STREAMS,
                                             [x.data_ptr() + po * fsz for x in self.outs], [m] * self.STREAMS))
             po += m
+        self.out_frames = po
         torch.cuda.synchronize()
 
     def step(self, s):
@@ -495,6 +515,9 @@ class AudioManyWorkload(AudioWorkload):
             r.reset()
         for c in self.calls:
             c.run(self.stream)
+
+    def outputs(self, s):
+        return [("resampled", [x[:self.out_frames] for x in self.outs])]
 
     def config(self, world):
         return {"workload": "%s, %d independent streams, a step = 10 s of each in buffers of %d frames (%d launches of %d streams)"
@@ -537,6 +560,12 @@ class AudioConvertWorkload:
             m = self.c.get_out_frames(n)
             self.c.samples(self.sig.data_ptr() + o * self.CH * 4, n, self.out.data_ptr() + po * self.CH * 2, m, self.stream)
             po += m
+        self.out_frames = po
+
+    def outputs(self, s):
+        """The S16 frames of the last step.  The converter's dither state runs on from step to step, and the untimed pre-heat runs as many
+        steps as fit in its time: the dithered low bits differ from run to run, the rest does not."""
+        return [("converted", [self.out[:self.out_frames]])]
 
     def config(self, world):
         return {"workload": "SURVEY 8(f)4: audioconvert F32LE 48000 Hz -> S16LE 44100 Hz stereo (tpdf dither, Kaiser resampler inside the converter), "
@@ -575,6 +604,10 @@ class StubWorkload:
 
     def step(self, s):
         time.sleep(0.001 * (1 + self.rank))
+
+    def outputs(self, s):
+        import torch
+        return [("stub", [torch.arange(64, dtype=torch.float64) + 1000 * self.rank + s])]
 
     def config(self, world):
         return {"workload": "stub", "parallelism": "stream-per-gpu x%d" % world}
@@ -650,6 +683,35 @@ def stored_traffic(name, frames_per_launch=None):
             except Exception:
                 pass
     return None, None
+
+
+DUMP_BYTES = 48 << 20      # all arrays of one --dump-outputs together
+
+
+def dump_outputs(named, out_dir):
+    """Writes [(name, [buffers])] (a workload's outputs(s): what a caller of the timed path receives) as out_dir/<name>.npy, one row per buffer,
+    in float32 (float64 for float64 buffers).  Buffers larger than their share of DUMP_BYTES are sampled at positions drawn from a fixed seed,
+    the same positions in every run with the same arguments.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    out_dtype = lambda t: torch.float64 if t.dtype == torch.float64 else torch.float32
+    per_value = sum(len(bufs) * (8 if out_dtype(bufs[0]) == torch.float64 else 4) for _, bufs in named)
+    share = max(1, DUMP_BYTES // per_value)          # values kept of each buffer
+    rng = np.random.default_rng(20261016)
+    shapes = {}
+    for name, bufs in named:
+        rows = []
+        for t in bufs:
+            t = t.reshape(-1)
+            if t.numel() > share:
+                pos = np.sort(rng.choice(t.numel(), share, replace=False))
+                t = t[torch.from_numpy(pos).to(t.device)]
+            rows.append(t.to(out_dtype(t)).cpu().numpy())
+        arr = np.stack(rows)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        shapes[name] = list(arr.shape)
+    return shapes
 
 
 def element_env():
@@ -774,8 +836,12 @@ def main():
     ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=None)
     ap.add_argument("--config", default="c2", help="c2 (headline) | c1 | c3 | c4 | c4opaque | c4audio | c4audiomany | c5 | c4a | f2gamma | f2p010out | f2p010in | f4audioconv | f5encode16 | f8scale | f8pack | f8swizzle | f6p010nv12 | f6p010bgra | f6p010p010 | f6nv12i420")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="c2: skip the batch-1 / element numbers reported beside the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the headline: c2's secondary section and the reference's CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (a fixed sample of at most 48 MiB) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the reference's CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full, c2: skip the batch-1 / element numbers reported beside the headline")
     ap.add_argument("--preheat-ms", type=float, default=60.0,
                     help="untimed sustained load before the W warmup steps: from idle an MI355X needs 20-30 ms of load "
                          "to reach its steady rate (scripts/clock_ramp.py, profiles/r01_clock_ramp.log)")
@@ -862,6 +928,9 @@ def main():
     sync()
     wall = time.perf_counter() - t0
     ev_ms = ev0.elapsed_time(ev1) if not cpu_mode else t_rank * 1e3
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(wl.outputs(steps - 1), args.dump_outputs)
+        print("bench.py: outputs of step %d written to %s: %s" % (steps - 1, args.dump_outputs, shapes), file=sys.stderr)
 
     ctl_dev = torch.device("cpu") if shared_gpu else dev
     wall_max, total_units = reduce_job(wall, steps * wl.units_per_step, ctl_dev, distributed)
@@ -898,9 +967,9 @@ def main():
                                "a launcher check, NOT a %d-GPU number" % (world, torch.cuda.device_count(), world))
         if hasattr(wl, "flops_per_step"):
             line["roofline"]["gflops"] = round(wl.flops_per_step * steps / (ev_ms * 1e-3) / 1e9, 1)
-        if world == 1 and args.config == "c2" and not args.no_secondary and not cpu_mode and not args.size and not args.batch:
+        if args.full and world == 1 and args.config == "c2" and not args.no_secondary and not cpu_mode and not args.size and not args.batch:
             line["secondary"] = secondary_c2(wl, sync)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = wl.cpu_baseline()
             except Exception as e:  # the baseline is a report, never a reason to fail the bench

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 O=gpurun_out/r06; mkdir -p $O
 for i in 1 2; do
-  timeout 400 python bench.py --no-cpu-baseline 2>$O/bench_adaptive_$i.err | tail -1 > $O/bench_adaptive_$i.json
+  timeout 400 python bench.py --full --no-cpu-baseline 2>$O/bench_adaptive_$i.err | tail -1 > $O/bench_adaptive_$i.json
   python - $O/bench_adaptive_$i.json <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[1]).read()); s=j.get("secondary",{})

@@ -4,7 +4,7 @@
 cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/.."
 O=gpurun_out/r06; mkdir -p $O
 for p in 0 1 2 3 4; do
-  GSTAMD_STORE_POLICY=$p timeout 300 python bench.py --no-cpu-baseline 2>/dev/null | tail -1 > $O/store_policy_$p.json
+  GSTAMD_STORE_POLICY=$p timeout 300 python bench.py --full --no-cpu-baseline 2>/dev/null | tail -1 > $O/store_policy_$p.json
   python - $p $O/store_policy_$p.json <<'PY'
 import json,sys
 j=json.loads(open(sys.argv[2]).read()); s=j.get("secondary",{})

@@ -1267,13 +1267,14 @@ def test_amdhipvideotestsrc_paints_the_reference_sources_frames_in_hbm(gst_env, 
     a, b = np.fromfile(fa, np.uint8), np.fromfile(fb, np.uint8)
     assert a.size == b.size and a.size > 0
     if env.get("GSTAMD_RUNTIME") == "1.29" or pattern in ("smpte", "colors", "blink"):
-        import cases
-        from oracle import ref
-        ri = ref.video_info(fmt, w, h)
+        from gstreamer_amd import video as V
+        # the default layout: the library's video_info, pinned against the reference's gst_video_info_set_format elsewhere
+        vi = V.video_info(fmt, w, h)
+        strides, offsets = [int(vi.stride[i]) for i in range(4)], [int(vi.offset[i]) for i in range(4)]
         for k in range(n):
             fa_k, fb_k = a.reshape(n, -1)[k], b.reshape(n, -1)[k]
-            va = cases.visible_bytes(fmt, w, h, list(ri["stride"]), list(ri["offset"]), fa_k)
-            vb = cases.visible_bytes(fmt, w, h, list(ri["stride"]), list(ri["offset"]), fb_k)
+            va = cases.visible_bytes(fmt, w, h, strides, offsets, fa_k)
+            vb = cases.visible_bytes(fmt, w, h, strides, offsets, fb_k)
             assert (va == vb).all(), (pattern, fmt, k, int((va != vb).sum()))
 
 
