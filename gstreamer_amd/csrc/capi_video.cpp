@@ -9,7 +9,6 @@
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <array>
 #include <vector>
 
 #include "../../include/gstamd_video.h"
@@ -705,7 +704,7 @@ static int bind_scratch (GstAmdVideoConverter *c, void *stream)
 
 static int frame_planes_plan_order (GstAmdVideoConverter *c, const void *const src_planes[GSTAMD_VIDEO_MAX_PLANES],
     const int32_t src_stride[GSTAMD_VIDEO_MAX_PLANES], void *const dest_planes[GSTAMD_VIDEO_MAX_PLANES],
-    const int32_t dest_stride[GSTAMD_VIDEO_MAX_PLANES], void *stream_);
+    const int32_t dest_stride[GSTAMD_VIDEO_MAX_PLANES], void *stream_, bool dither = true);
 // the chain up to a packed 4-byte image: unpack, chroma upsample, scale, matrix, alpha, byte order
 static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t *dst, int dstride, hipStream_t stream);
 static int convert_rect (GstAmdVideoConverter *c, const Planes &pl, void *const dest_planes[GSTAMD_VIDEO_MAX_PLANES],
@@ -1079,9 +1078,21 @@ int gstamd_video_converter_frame_planes (GstAmdVideoConverter *c, const void *co
   return frame_planes_plan_order (c, sp, src_stride ? ss : nullptr, dp, dest_stride ? ds : nullptr, stream);
 }
 
+// the dither stage (video_dither.h) over the converted rectangle of the packed destination whose first plane is `plane0`: the last step of
+// frame_planes_plan_order, which a frame list runs frame by frame after the list's launches (gstamd_video_converter_frames)
+static int dither_frame (GstAmdVideoConverter *c, uint8_t *plane0, int stride, hipStream_t stream)
+{
+  const VideoPlan &p = c->plan;
+  if (!p.dither.on)
+    return GSTAMD_OK;
+  uint8_t *rect = plane0 + plane_origin (p.fout, 0, p.rect.out_x, p.rect.out_y, stride);
+  const hipError_t de = launch_dither4 (p.dither, rect, stride, p.out_info.width, p.out_info.height, stream, c->ed_carry);
+  return de == hipSuccess ? GSTAMD_OK : hip_fail (de, "k_dither4");
+}
+
 static int frame_planes_plan_order (GstAmdVideoConverter *c, const void *const src_planes[GSTAMD_VIDEO_MAX_PLANES],
     const int32_t src_stride[GSTAMD_VIDEO_MAX_PLANES], void *const dest_planes[GSTAMD_VIDEO_MAX_PLANES],
-    const int32_t dest_stride[GSTAMD_VIDEO_MAX_PLANES], void *stream_)
+    const int32_t dest_stride[GSTAMD_VIDEO_MAX_PLANES], void *stream_, bool dither)
 {
   if (!c || !src_planes || !dest_planes || !src_planes[0] || !dest_planes[0])
     return set_error (GSTAMD_ERR_INVALID, "NULL converter or frame");
@@ -1172,13 +1183,7 @@ static int frame_planes_plan_order (GstAmdVideoConverter *c, const void *const s
       return hip_fail (be, "k_fill_border");
   }
   r = convert_rect (c, pl, dest_rect, dest_rect_stride, stream);
-  if (r == GSTAMD_OK && p.dither.on) {
-    /* the dither stage (video_dither.h) over the converted rectangle of the packed destination */
-    hipError_t de = launch_dither4 (p.dither, (uint8_t *) dest_rect[0], dest_rect_stride[0], p.out_info.width, p.out_info.height, stream, c->ed_carry);
-    if (de != hipSuccess)
-      return hip_fail (de, "k_dither4");
-  }
-  return r;
+  return r == GSTAMD_OK && dither ? dither_frame (c, (uint8_t *) dest_planes[0], dest_rect_stride[0], stream) : r;
 }
 
 // the conversion proper: source planes already at the crop origin, destination planes at the rectangle origin
@@ -1288,8 +1293,7 @@ static int convert_rect (GstAmdVideoConverter *c, const Planes &pl, void *const 
     if (p.fout->kind == UNPACK_PACKED3 && fast_pair_usable (p, pl, planes[0], strides[0], 4)) {
       /* NV12 / NV21 -> RGB / BGR, same size: the line-pair kernel stores the 3-byte pixels itself (12 bytes per lane and line) */
       const FastParams fp = make_fast_params (p, true);
-      const uint8_t *y = pl.p[0], *uv = pl.p[1];
-      hipError_t e = launch_convert_pair (fp, p.front.chroma_h, 1, &y, &uv, &planes[0], pl.stride[0], pl.stride[1], strides[0], stream);
+      hipError_t e = launch_convert_pair (fp, p.front.chroma_h, pl.p[0], pl.p[1], planes[0], pl.stride[0], pl.stride[1], strides[0], stream);
       return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert_pair(rgb24)");
     }
     if (p.fast_enc420 && ((uintptr_t) pl.p[0] % 16) == 0 && (pl.stride[0] % 16) == 0 && ((uintptr_t) planes[0] % 4) == 0 && (strides[0] % 4) == 0 &&
@@ -1406,12 +1410,25 @@ static bool col_usable (const GstAmdVideoConverter *c, const Planes &pl, const C
       (p.front.kind == UNPACK_SEMI || pl.stride[p.front.u_plane] == pl.stride[p.front.v_plane]);
 }
 
-// n frames (source plane pointers src[f][0 .. 2], destinations dst[f]) of the strides of `pl`: launches of up to GSTAMD_COL_MAX_FRAMES frames
-static hipError_t col_launch (GstAmdVideoConverter *c, int n, const void *const (*src)[3], uint8_t *const *dst, const Planes &pl, int dstride, const ColorParams &post,
-    const PostFast &pf, hipStream_t stream)
+// one frame, or the armed frame list behind it (video_kernels.hip) when every destination of it is aligned like this one: launches of up to
+// GSTAMD_COL_MAX_FRAMES frames
+static hipError_t col_launch (GstAmdVideoConverter *c, const Planes &pl, uint8_t *dst, int dstride, const ColorParams &post, const PostFast &pf, hipStream_t stream)
 {
   const VideoPlan &p = c->plan;
   const bool semi = p.front.kind == UNPACK_SEMI;
+  /* the destination rows launch_scale_col refuses, decided before the list is taken (col_ok: the kernel form, its waves and LDS fit) */
+  const int unit = 4 * c->col_form.opl;
+  if ((dstride % unit) != 0 || ((uintptr_t) dst % unit) != 0)
+    return hipErrorNotSupported;
+  int n;
+  const FrameDeltas &fl = video_frame_list_peek (pl.p[0], dst, &n);
+  for (int f = 1; f < n; f++)
+    if (fl.d[f] % unit != 0)
+      n = 1;
+  if (n > 1)
+    (void) video_frame_list_for (pl.p[0], dst, &n, GSTAMD_COL_MAX_FRAMES);
+  else
+    video_frame_list_touch (dst);
   ColParams q;
   memset ((void *) &q, 0, sizeof (q));
   q.ystride = pl.stride[0];
@@ -1433,10 +1450,11 @@ static hipError_t col_launch (GstAmdVideoConverter *c, int n, const void *const 
     ColFrames fr;
     memset ((void *) &fr, 0, sizeof (fr));
     for (int f = 0; f < nb; f++) {
-      fr.y[f] = (const uint8_t *) src[base + f][0];
-      fr.c0[f] = (const uint8_t *) (semi ? src[base + f][1] : src[base + f][p.front.u_plane]);
-      fr.c1[f] = (const uint8_t *) (semi ? src[base + f][1] : src[base + f][p.front.v_plane]);
-      fr.dst[f] = dst[base + f];
+      const long long s = fl.s[base + f];
+      fr.y[f] = pl.p[0] + s;
+      fr.c0[f] = (semi ? pl.p[1] : pl.p[p.front.u_plane]) + s;
+      fr.c1[f] = (semi ? pl.p[1] : pl.p[p.front.v_plane]) + s;
+      fr.dst[f] = dst + fl.d[base + f];
     }
 #ifdef GSTAMD_COL_TRACE
     /* profiling builds: cycles per phase of the walk, averaged over the waves of the launch (stderr) */
@@ -1669,8 +1687,7 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
       fp.lut_keep = c->post_lut_keep;
       c->post_lut_done = true;
     }
-    const uint8_t *y = pl.p[0], *uv = pl.p[1];
-    e = launch_convert_pair (fp, p.front.chroma_h, 1, &y, &uv, &dst, pl.stride[0], pl.stride[1], dstride, stream);
+    e = launch_convert_pair (fp, p.front.chroma_h, pl.p[0], pl.p[1], dst, pl.stride[0], pl.stride[1], dstride, stream);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert_pair");
   }
   if (p.fast_420p && ((uintptr_t) pl.p[0] % 8) == 0 && (pl.stride[0] % 8) == 0 && ((uintptr_t) pl.p[1] % 4) == 0 && ((uintptr_t) pl.p[2] % 4) == 0 &&
@@ -1819,9 +1836,7 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
         fast_params_finish (fp, p.matrix.p, ident, p.front.u_plane);
         fp.crow_lo = -(p.rect.in_y >> 1);
         fp.crow_hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
-        const uint8_t *y = pl.p[0], *uv = pl.p[1];
-        uint8_t *img = c->pre_img;
-        if ((e = launch_convert_pair (fp, p.front.chroma_h, 1, &y, &uv, &img, pl.stride[0], pl.stride[1], in_w * 4, stream)) != hipSuccess)
+        if ((e = launch_convert_pair (fp, p.front.chroma_h, pl.p[0], pl.p[1], c->pre_img, pl.stride[0], pl.stride[1], in_w * 4, stream)) != hipSuccess)
           return hip_fail (e, "k_convert_pair(source size)");
       } else
       if ((e = launch_convert (p.front, pl, c->vpair_dev, pre, ident, c->pre_img, in_w * 4, stream, 0)) != hipSuccess)
@@ -1859,8 +1874,7 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "scale pass");
   }
   if (col_usable (c, pl, pre)) {
-    const void *sp[3] = {pl.p[0], pl.p[1], pl.p[2]};
-    e = col_launch (c, 1, &sp, &dst, pl, dstride, post, pf, stream);
+    e = col_launch (c, pl, dst, dstride, post, pf, stream);
     if (e == hipSuccess)
       return GSTAMD_OK;
     if (e != hipErrorNotSupported)
@@ -1966,17 +1980,23 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
   return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "scale pass 2");
 }
 
-int gstamd_video_converter_frame (GstAmdVideoConverter *c, const void *src, void *dest, void *stream)
+// one frame of the plan's VideoInfos; dither = false leaves out the trailing dither stage (dither_frame)
+static int convert_frame (GstAmdVideoConverter *c, const void *src, void *dest, void *stream, bool dither)
 {
-  if (!c || !src || !dest)
-    return set_error (GSTAMD_ERR_INVALID, "NULL converter or frame");
   const void *sp[GSTAMD_VIDEO_MAX_PLANES] = {nullptr, nullptr, nullptr, nullptr};
   void *dp[GSTAMD_VIDEO_MAX_PLANES] = {nullptr, nullptr, nullptr, nullptr};
   for (int i = 0; i < c->plan.in_info.n_planes; i++)
     sp[i] = (const uint8_t *) src + c->plan.in_info.offset[i];
   for (int i = 0; i < c->plan.out_info.n_planes; i++)
     dp[i] = (uint8_t *) dest + c->plan.out_info.offset[i];
-  return frame_planes_plan_order (c, sp, nullptr, dp, nullptr, stream);
+  return frame_planes_plan_order (c, sp, nullptr, dp, nullptr, stream, dither);
+}
+
+int gstamd_video_converter_frame (GstAmdVideoConverter *c, const void *src, void *dest, void *stream)
+{
+  if (!c || !src || !dest)
+    return set_error (GSTAMD_ERR_INVALID, "NULL converter or frame");
+  return convert_frame (c, src, dest, stream, true);
 }
 
 // frames [0, n) of a list one by one on the caller's stream.  (Round 5 tried fanning them out over four internal streams, forked from and joined
@@ -1996,6 +2016,9 @@ int gstamd_video_converter_frames (GstAmdVideoConverter *c, int n_frames, const 
 {
   if (!c || n_frames < 0 || (n_frames > 0 && (!src || !dest)))
     return set_error (GSTAMD_ERR_INVALID, "NULL converter or frame list");
+  for (int i = 0; i < n_frames; i++)
+    if (!src[i] || !dest[i])
+      return set_error (GSTAMD_ERR_INVALID, "NULL frame in list");
   if (n_frames == 0)
     return GSTAMD_OK;
   const VideoPlan &p = c->plan;
@@ -2030,105 +2053,11 @@ int gstamd_video_converter_frames (GstAmdVideoConverter *c, int n_frames, const 
   DeepPackParams dsp_list;
   const bool deep_pack_list = p.gamma.on && !c->hook_on && !tuning_on ("GSTAMD_NO_DEEP_SCALE_PACK") &&
       ((deep_pack_usable (c, &dsp_list) && !c->sub_out->plan.rect.fill) || deep_scale_pack16_plan_ok (p, &dsp_list));        /* k_deep_scale_pack / _pack16: one kernel, takes lists */
-  if (p.gamma.on && !p.gamma.planes_fast && !enc16_list && !deep_pack_list)
-    return frames_one_by_one (c, n_frames, src, dest, stream_);
-  /* one launch for the whole list when the line-pair kernel applies to every frame */
-  bool all_fast = true;
-  std::vector<const uint8_t *> y (n_frames), uv (n_frames);
-  std::vector<uint8_t *> d (n_frames);
-  for (int i = 0; i < n_frames && all_fast; i++) {
-    if (!src[i] || !dest[i])
-      return set_error (GSTAMD_ERR_INVALID, "NULL frame in list");
-    Planes pl;
-    memset (&pl, 0, sizeof (pl));
-    pl.p[0] = (const uint8_t *) src[i] + p.in_info.offset[0];
-    pl.p[1] = (const uint8_t *) src[i] + p.in_info.offset[1];
-    pl.stride[0] = p.in_info.stride[0];
-    pl.stride[1] = p.in_info.stride[1];
-    d[i] = (uint8_t *) dest[i] + p.out_info.offset[0];
-    all_fast = (p.fout->kind == UNPACK_PACKED4 || p.fout->kind == UNPACK_PACKED3) &&
-        fast_pair_usable (p, pl, d[i], p.out_info.stride[0], p.fout->kind == UNPACK_PACKED3 ? 4 : 16) && p.rect.in_x == 0 && p.rect.in_y == 0 && p.rect.out_x == 0 &&
-        p.rect.out_y == 0 && !p.rect.fill;
-    y[i] = pl.p[0];
-    uv[i] = pl.p[1];
-  }
-  if (all_fast) {
-    FastParams fp = make_fast_params (p, p.fout->kind == UNPACK_PACKED3);
-    if (c->post_lut) {          /* this converter is the direct conversion of a collapsed gamma remap (see above) */
-      fp.lut = c->post_lut;
-      fp.lut_keep = c->post_lut_keep;
-      c->post_lut_done = true;
-    }
-    hipError_t e = launch_convert_pair (fp, p.front.chroma_h, n_frames, y.data (), uv.data (), d.data (), p.in_info.stride[0],
-        p.in_info.stride[1], p.out_info.stride[0], (hipStream_t) stream_);
-    for (int i = 0; i < n_frames && e == hipSuccess && p.dither.on; i++)
-      e = launch_dither4 (p.dither, d[i], p.out_info.stride[0], p.out_info.width, p.out_info.height, (hipStream_t) stream_, c->ed_carry);
-    c->list_launches = p.dither.on ? 0 : (n_frames + 31) / 32;
-    return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert_pair(batch)");
-  }
-  /* one launch for the whole list through the bilinear 4:2:0 kernel as well (k_bilinear420_rows takes the frames as one grid) */
-  BilParams bp;
-  if (!p.rect.fill && p.rect.in_x == 0 && p.rect.in_y == 0 && p.rect.out_x == 0 && p.rect.out_y == 0 && bilinear420_params (c, &bp) && bp.rows != 0) {
-    std::vector<Planes> pls (n_frames);
-    bool ok = true;
-    for (int i = 0; i < n_frames && ok; i++) {
-      if (!src[i] || !dest[i])
-        return set_error (GSTAMD_ERR_INVALID, "NULL frame in list");
-      memset (&pls[i], 0, sizeof (Planes));
-      for (int k = 0; k < p.in_info.n_planes && k < 3; k++) {
-        pls[i].p[k] = (const uint8_t *) src[i] + p.in_info.offset[k];
-        pls[i].stride[k] = p.in_info.stride[k];
-      }
-      d[i] = (uint8_t *) dest[i] + p.out_info.offset[0];
-      ok = ((uintptr_t) d[i] % 4) == 0;
-    }
-    if (ok && (p.out_info.stride[0] % 4) == 0) {
-      hipError_t e = launch_bilinear420_frames (bp, p.front.chroma_h, n_frames, pls.data (), d.data (), p.out_info.stride[0], (hipStream_t) stream_);
-      for (int i = 0; i < n_frames && e == hipSuccess && p.dither.on; i++)
-        e = launch_dither4 (p.dither, d[i], p.out_info.stride[0], p.out_info.width, p.out_info.height, (hipStream_t) stream_, c->ed_carry);
-      if (e != hipErrorNotSupported) {
-        c->list_launches = p.dither.on ? 0 : 1;
-        return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_bilinear420(batch)");
-      }
-    }
-  }
-  /* ... and through the column-walk scaler (k_scale_col takes the frames as the grid's third dimension) */
-  if (c->col_ok && !p.rect.fill && p.rect.in_x == 0 && p.rect.in_y == 0 && p.rect.out_x == 0 && p.rect.out_y == 0 && !p.out_planar && !p.plane_mode &&
-      p.fout->kind == UNPACK_PACKED4 && p.fout->hi_depth == 0 && !p.matrix_before_scale) {
-    Planes pl0;
-    memset (&pl0, 0, sizeof (pl0));
-    for (int k = 0; k < p.in_info.n_planes && k < 3; k++)
-      pl0.stride[k] = p.in_info.stride[k];
-    ColorParams none_c, color;
-    memset (&none_c, 0, sizeof (none_c));
-    color.matrix = p.matrix;
-    color.alpha_kind = p.post.alpha_kind;
-    color.alpha_value = p.post.alpha_value;
-    if (col_usable (c, pl0, none_c)) {
-      std::vector<std::array<const void *, 3>> sp (n_frames);
-      for (int i = 0; i < n_frames; i++) {
-        if (!src[i] || !dest[i])
-          return set_error (GSTAMD_ERR_INVALID, "NULL frame in list");
-        for (int k = 0; k < 3; k++)
-          sp[i][k] = k < p.in_info.n_planes ? (const uint8_t *) src[i] + p.in_info.offset[k] : nullptr;
-        d[i] = (uint8_t *) dest[i] + p.out_info.offset[0];
-      }
-      PostFast pf;
-      pf.use = p.fast_post ? 1 : 0;
-      pf.fp = make_fast_params (p);
-      hipError_t e = col_launch (c, n_frames, (const void *const (*)[3]) sp.data (), d.data (), pl0, p.out_info.stride[0], color, pf, (hipStream_t) stream_);
-      for (int i = 0; i < n_frames && e == hipSuccess && p.dither.on; i++)
-        e = launch_dither4 (p.dither, d[i], p.out_info.stride[0], p.out_info.width, p.out_info.height, (hipStream_t) stream_, c->ed_carry);
-      if (e != hipErrorNotSupported) {
-        c->list_launches = p.dither.on ? 0 : (n_frames + GSTAMD_COL_MAX_FRAMES - 1) / GSTAMD_COL_MAX_FRAMES;
-        return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_scale_col(batch)");
-      }
-    }
-  }
-  /* plans that convert a frame in ONE launch of a kernel that takes frame lists (video_kernels.hip: the list is the grid's third
-     dimension): frame `base` is converted with the list of up to 32 frames behind it armed; the launcher says whether it took the list */
+  /* plans that convert a frame with kernels that take frame lists (video_kernels.hip: the list is the grid's third dimension): frame `base` is
+     converted with the list of up to 32 frames behind it armed; the launchers say whether they took the list.  The dither stage takes no list:
+     it runs frame by frame after the list's launches, and such a list counts no list launches */
   int base = 0;
-  if (!p.rect.fill && !p.dither.on && (!p.gamma.on || p.gamma.planes_fast || enc16_list || deep_pack_list)) {
+  if (!p.rect.fill && (!p.gamma.on || p.gamma.planes_fast || enc16_list || deep_pack_list)) {
     /* a plan that scales into the pack image and packs from it with list-taking kernels (k_plane_quad + k_encode420 / k_convert_pack: raw4_pack) gets
        one image per frame of the list - up to 1 GiB of them - so that both launches take the list */
     if (c->raw4_pack && c->pk_img && !c->hook_on) {
@@ -2149,22 +2078,20 @@ int gstamd_video_converter_frames (GstAmdVideoConverter *c, int n_frames, const 
       int nb = std::min (n_frames - base, 32);
       if (c->raw4_pack && c->pk_img && c->pk_img_frames > 1)
         nb = std::min (nb, c->pk_img_frames);
-      for (int i = 0; i < nb; i++)
-        if (!src[base + i] || !dest[base + i])
-          return set_error (GSTAMD_ERR_INVALID, "NULL frame in list");
       video_frame_list_begin (nb, src + base, dest + base, p.in_info.size, p.out_info.size);
       if (c->pk_img && c->pk_img_frames >= nb)
         video_frame_list_scratch (c->pk_img, pk_img_bytes (p));
-      r = gstamd_video_converter_frame (c, src[base], dest[base], stream_);
+      r = convert_frame (c, src[base], dest[base], stream_, false);
       const int used = video_frame_list_end ();
+      const int done = used ? nb : 1;          /* 1: this plan's kernels do not take the list - frame by frame from here */
+      for (int i = 0; i < done && r == GSTAMD_OK; i++)
+        r = dither_frame (c, (uint8_t *) dest[base + i] + p.out_info.offset[0], p.out_info.stride[0], (hipStream_t) stream_);
       if (r != GSTAMD_OK)
         return r;
-      if (!used) {
-        base++;                 /* this plan's kernels do not take lists: frame by frame from here */
+      base += done;
+      if (!used)
         break;
-      }
-      c->list_launches += used;
-      base += nb;
+      c->list_launches += p.dither.on ? 0 : used;
     }
   }
   return frames_one_by_one (c, n_frames - base, src + base, dest + base, stream_);

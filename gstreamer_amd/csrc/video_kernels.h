@@ -26,7 +26,8 @@ struct FrameDeltas {
   long long s[GSTAMD_MAX_BATCH], d[GSTAMD_MAX_BATCH];
 };
 #define GSTAMD_FRAME_Z const long long fls_ = fl.s[blockIdx.z], fld_ = fl.d[blockIdx.z]
-const FrameDeltas &video_frame_list_for (const void *sp, const void *dp, int *nz);
+const FrameDeltas &video_frame_list_for (const void *sp, const void *dp, int *nz, int per_launch = GSTAMD_MAX_BATCH);
+const FrameDeltas &video_frame_list_peek (const void *sp, const void *dp, int *nz);
 
 hipError_t launch_convert (const FrontParams &f, const Planes &pl, const int *vpair_dev, const ColorParams &color,
     const int pack_pos[4], uint8_t *dst, int dstride, hipStream_t stream, int extra_rows = 0);
@@ -63,8 +64,9 @@ hipError_t launch_scale16 (const Deep16Image &im, const ScaleDev &sd, bool horiz
     const PostParams *post, hipStream_t stream);
 
 struct FastParams;
-hipError_t launch_convert_pair (const FastParams &fp, int chroma_h, int n_frames, const uint8_t *const *y, const uint8_t *const *uv,
-    uint8_t *const *dst, int ystride, int uvstride, int dstride, hipStream_t stream);
+// one frame, or the armed frame list behind it when every frame of it is aligned like this one
+hipError_t launch_convert_pair (const FastParams &fp, int chroma_h, const uint8_t *y, const uint8_t *uv, uint8_t *dst, int ystride, int uvstride,
+    int dstride, hipStream_t stream);
 
 hipError_t launch_scale_from_front (bool horizontal, const FrontParams &f, const Planes &pl, const int *vpair_dev,
     const ColorParams &pre, const ScaleDev &sd, uint8_t *dst, int dstride, bool final, const ColorParams &post,
@@ -81,12 +83,11 @@ hipError_t launch_scale2x2_from_front (const FrontParams &f, const Planes &pl, c
 hipError_t launch_hscale420_reg (const H420RegParams &p, int chroma_h, int nw, int n_taps, hipStream_t stream);
 hipError_t launch_convert422 (const Fast422Params &p, const uint8_t *src, int sstride, uint8_t *dst, int dstride, hipStream_t stream, bool ayuv = false);
 hipError_t launch_convert420p (const Fast420pParams &p, uint8_t *dst, int dstride, hipStream_t stream);
+// one frame, or the armed frame list behind it in one launch when k_bilinear420_half / k_bilinear420_rows take every frame of it
 hipError_t launch_bilinear420 (const BilParams &bp, int chroma_h, const Planes &pl, uint8_t *dst, int dstride, hipStream_t stream);
-// n frames of the same geometry in as few launches as the kernel allows (one, when k_bilinear420_rows takes them)
 // the exact halving (BilParams::half) on frames whose rows are 16-byte aligned: video_bilinear_half.hip
 bool bilinear420_half_usable (const BilParams &bp, int n, const Planes *pl, uint8_t *const *dst, int dstride);
 hipError_t launch_bilinear420_half (const BilParams &bp, int chroma_h, int n, const Planes *pl, uint8_t *const *dst, int dstride, hipStream_t stream);
-hipError_t launch_bilinear420_frames (const BilParams &bp, int chroma_h, int n, const Planes *pl, uint8_t *const *dst, int dstride, hipStream_t stream);
 hipError_t launch_plane_simple (int kind, const uint8_t *src, int sstride, uint8_t *dst, int dstride, int n_elems, int ow, int oh, hipStream_t stream);
 hipError_t launch_plane_pass (bool horizontal, const ScaleDev &sd, const uint8_t *src, int sstride, uint8_t *dst, int dstride, int n_elems,
     int ow, int oh, hipStream_t stream);

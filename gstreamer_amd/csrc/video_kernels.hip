@@ -97,8 +97,10 @@ void video_frame_list_touch (const void *dp)
   if (c.armed && ((d8 >= c.dst0 && d8 < c.dst0 + c.dst_size) || (c.scr0 && d8 >= c.scr0 && d8 < c.scr0 + c.scr_stride)))
     c.mixed = true;
 }
-// the list for a launch whose source / destination pointers are sp / dp (NULL: not a frame's plane, or no list): *nz = frames
-static const FrameDeltas &frame_list_for (const void *sp, const void *dp, int *nz)
+// the list a launch whose source / destination pointers are sp / dp would take (NULL: not a frame's plane, or no list), without taking it:
+// *nz = frames.  A launcher that serves only some lists (every frame aligned like frame 0) looks first, then takes the list (frame_list_for)
+// or serves frame 0 alone (video_frame_list_touch).
+const FrameDeltas &video_frame_list_peek (const void *sp, const void *dp, int *nz)
 {
   static const FrameDeltas none = {};
   FrameListCtx &c = g_frame_list;
@@ -109,7 +111,6 @@ static const FrameDeltas &frame_list_for (const void *sp, const void *dp, int *n
   const bool s_frame = s8 >= c.src0 && s8 < c.src0 + c.src_size, d_frame = d8 >= c.dst0 && d8 < c.dst0 + c.dst_size;
   const bool s_scr = c.scr0 && s8 >= c.scr0 && s8 < c.scr0 + c.scr_stride, d_scr = c.scr0 && d8 >= c.scr0 && d8 < c.scr0 + c.scr_stride;
   if (s_frame && d_frame) {
-    c.used++;
     *nz = c.n;
     return c.fd;
   }
@@ -118,17 +119,25 @@ static const FrameDeltas &frame_list_for (const void *sp, const void *dp, int *n
       c.tmp.s[i] = s_frame ? c.fd.s[i] : (long long) (i * c.scr_stride);
       c.tmp.d[i] = d_frame ? c.fd.d[i] : (long long) (i * c.scr_stride);
     }
-    c.used++;
     *nz = c.n;
     return c.tmp;
   }
-  if (d_scr || d_frame)
-    c.mixed = true;             /* a kernel that writes frame 0's picture or scratch image and cannot be rebased: the list is not served by launches alone */
   return none;
 }
+// ... and takes it: the list counts one launch per per_launch frames.  No list: a kernel that writes frame 0's picture or scratch image and cannot be
+// rebased makes the list one that launches alone do not serve.
+static const FrameDeltas &frame_list_for (const void *sp, const void *dp, int *nz, int per_launch = GSTAMD_MAX_BATCH)
+{
+  const FrameDeltas &fl = video_frame_list_peek (sp, dp, nz);
+  if (*nz > 1)
+    g_frame_list.used += (*nz + per_launch - 1) / per_launch;
+  else
+    video_frame_list_touch (dp);
+  return fl;
+}
 // (GSTAMD_FRAME_Z: video_kernels.h)
-// the same for launchers of other compilation units (video_deep_pack.hip)
-const FrameDeltas &video_frame_list_for (const void *sp, const void *dp, int *nz) { return frame_list_for (sp, dp, nz); }
+// the same for launchers of other compilation units (video_deep_pack.hip, capi_video.cpp)
+const FrameDeltas &video_frame_list_for (const void *sp, const void *dp, int *nz, int per_launch) { return frame_list_for (sp, dp, nz, per_launch); }
 
 template <int CH>
 __global__ __launch_bounds__ (256) void k_convert (FrontParams f, Planes pl, const int *__restrict__ vpair, ColorParams color,
@@ -1655,10 +1664,21 @@ static bool launch_fast (const FastParams &fp, const FrameBatch &batch, int n, h
   return launch_strip_variant<CH, 0> (fp, batch, n, K, v.set && v.order != 0, stream);
 }
 
-hipError_t launch_convert_pair (const FastParams &fp_in, int chroma_h, int n_frames, const uint8_t *const *y, const uint8_t *const *uv,
-    uint8_t *const *dst, int ystride, int uvstride, int dstride, hipStream_t stream)
+hipError_t launch_convert_pair (const FastParams &fp_in, int chroma_h, const uint8_t *y, const uint8_t *uv, uint8_t *dst, int ystride, int uvstride,
+    int dstride, hipStream_t stream)
 {
-  video_frame_list_touch (dst[0]);
+  /* the caller checked this frame's alignment (capi_video.cpp fast_pair_usable: planes 4 bytes, destination 16 - 4 for 3-byte pixels); a list is
+     served when every frame of it has that alignment, else this launch converts frame 0 alone */
+  int n_frames;
+  const FrameDeltas &fl = video_frame_list_peek (y, dst, &n_frames);
+  const int dalign = fp_in.px_bytes == 3 ? 4 : 16;
+  for (int i = 1; i < n_frames; i++)
+    if (fl.s[i] % 4 != 0 || fl.d[i] % dalign != 0)
+      n_frames = 1;
+  if (n_frames > 1)
+    (void) frame_list_for (y, dst, &n_frames);
+  else
+    video_frame_list_touch (dst);
   /* store policy (video_fast.h store16_policy): write-through for launches of few frames - what such a launch leaves dirty in the L2s is written back
      at its end, on the critical path of the next launch; a long list amortises that and takes the write-through streaming store (sc0 sc1 nt), the
      fastest of the five at 32 frames (profiles/r06/store_policy.md).  GSTAMD_STORE_POLICY pins it. */
@@ -1674,9 +1694,9 @@ hipError_t launch_convert_pair (const FastParams &fp_in, int chroma_h, int n_fra
     FrameBatch batch;
     memset (&batch, 0, sizeof (batch));
     for (int i = 0; i < n; i++) {
-      batch.y[i] = y[base + i];
-      batch.uv[i] = uv[base + i];
-      batch.dst[i] = dst[base + i];
+      batch.y[i] = y + fl.s[base + i];
+      batch.uv[i] = uv + fl.s[base + i];
+      batch.dst[i] = dst + fl.d[base + i];
     }
     batch.ystride = ystride;
     batch.uvstride = uvstride;
@@ -2134,34 +2154,45 @@ static hipError_t launch_bilinear420_rows (const BilParams &bp, int chroma_h, in
   return hipGetLastError ();
 }
 
-hipError_t launch_bilinear420_frames (const BilParams &bp, int chroma_h, int n, const Planes *pl, uint8_t *const *dst, int dstride, hipStream_t stream)
+// the rows kernel takes frames [0, n): every one vectorisable, the destinations 4-byte aligned (the caller checked frame 0's)
+static bool bilinear420_rows_usable (const BilParams &bp, int n, const Planes *pl, uint8_t *const *dst)
 {
-  video_frame_list_touch (dst[0]);
-  if (bilinear420_half_usable (bp, n, pl, dst, dstride))
-    return launch_bilinear420_half (bp, chroma_h, n, pl, dst, dstride, stream);
-  bool rows_ok = bp.rows != 0 && (bp.fp.width % 16) == 0 && bp.regular_pairs;
-  for (int f = 0; f < n && rows_ok; f++)
-    rows_ok = bil_vec_ok (bp, pl[f]) && pl[f].stride[0] == pl[0].stride[0] && pl[f].stride[1] == pl[0].stride[1] && pl[f].stride[2] == pl[0].stride[2];
-  if (rows_ok)
-    return launch_bilinear420_rows (bp, chroma_h, n, pl, dst, dstride, stream);
-  for (int f = 0; f < n; f++) {
-    const hipError_t e = launch_bilinear420 (bp, chroma_h, pl[f], dst[f], dstride, stream);
-    if (e != hipSuccess)
-      return e;
-  }
-  return hipSuccess;
+  bool ok = bp.rows != 0 && (bp.fp.width % 16) == 0 && bp.regular_pairs;
+  for (int f = 0; f < n && ok; f++)
+    ok = bil_vec_ok (bp, pl[f]) && aligned (dst[f], 4);
+  return ok;
 }
 
 hipError_t launch_bilinear420 (const BilParams &bp, int chroma_h, const Planes &pl, uint8_t *dst, int dstride, hipStream_t stream)
 {
-  video_frame_list_touch (dst);
-  if (bilinear420_half_usable (bp, 1, &pl, &dst, dstride))
-    return launch_bilinear420_half (bp, chroma_h, 1, &pl, &dst, dstride, stream);
+  int n;
+  const FrameDeltas &fl = video_frame_list_peek (pl.p[0], dst, &n);
+  Planes pls[GSTAMD_MAX_BATCH];
+  uint8_t *dsts[GSTAMD_MAX_BATCH];
+  for (int f = 0; f < n; f++) {
+    pls[f] = pl;
+    for (int k = 0; k < 3; k++)
+      if (pl.p[k])
+        pls[f].p[k] += fl.s[f];
+    dsts[f] = dst + fl.d[f];
+  }
+  bool half = bilinear420_half_usable (bp, n, pls, dsts, dstride), rows = !half && bilinear420_rows_usable (bp, n, pls, dsts);
+  if (n > 1 && !half && !rows) {
+    /* a list the list-taking kernels do not take as a whole: frame 0 alone, the caller goes on frame by frame */
+    n = 1;
+    half = bilinear420_half_usable (bp, 1, pls, dsts, dstride), rows = !half && bilinear420_rows_usable (bp, 1, pls, dsts);
+  }
+  if (n > 1)
+    (void) frame_list_for (pl.p[0], dst, &n);
+  else
+    video_frame_list_touch (dst);
+  if (half)
+    return launch_bilinear420_half (bp, chroma_h, n, pls, dsts, dstride, stream);
+  if (rows)
+    return launch_bilinear420_rows (bp, chroma_h, n, pls, dsts, dstride, stream);
   const int vec = bil_vec_ok (bp, pl);
   if (bp.planar && !vec)
     return hipErrorNotSupported;
-  if (bp.rows != 0 && vec && (bp.fp.width % 16) == 0 && bp.regular_pairs)
-    return launch_bilinear420_rows (bp, chroma_h, 1, &pl, &dst, dstride, stream);
   const int tiles_x = (bp.out_w + bp.tile_w - 1) / bp.tile_w;
   dim3 grid (wide_grid_blocks (tiles_x, bp.out_h));
   const size_t lds_bytes = bil_lds_words (bp.ylen) * 4;

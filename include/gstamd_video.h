@@ -332,7 +332,8 @@ const char *gstamd_video_test_pattern_describe (const GstAmdVideoTestPattern *pa
 void gstamd_video_test_pattern_free (GstAmdVideoTestPattern *pattern);
 
 /* How the last _frames call on this converter ran: the number of kernel launches that each served a whole list (or a
- * chunk of up to 32 / 16 frames of it) - 0 when the plan's kernels took the frames one by one.  What tests and the
+ * chunk of up to 32 / 16 frames of it) - 0 when the plan's kernels took the frames one by one, when a stage that takes no
+ * list (a dither pass) ran frame by frame after them, and for a call of one frame.  What tests and the
  * element's statistics read; no reference counterpart (the reference converts buffer lists buffer by buffer,
  * gstbasetransform.c default chain_list). */
 int gstamd_video_converter_list_launches (GstAmdVideoConverter *convert);
