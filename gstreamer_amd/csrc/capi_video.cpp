@@ -15,6 +15,7 @@
 #include "planner.h"
 #include "tuning.h"
 #include "video_kernels.h"
+#include "video_dispatch.h"
 #include "video_fast.h"
 #include "video_encode_fast.h"
 #include "video_scale420_fused.h"
@@ -260,26 +261,6 @@ static void col_geometry (const GstAmdVideoConverter *c, int n_frames, ColParams
   q->pubn = solo ? 0 : c->col.pubn;
 }
 
-static bool fast_pair_usable (const VideoPlan &p, const Planes &pl, const uint8_t *dst, int dstride, int dalign = 16)
-{
-  return p.passes.empty () && p.fast_pair && ((uintptr_t) dst % dalign) == 0 && (dstride % dalign) == 0 &&
-      ((uintptr_t) pl.p[0] % 4) == 0 && (pl.stride[0] % 4) == 0 && ((uintptr_t) pl.p[1] % 4) == 0 && (pl.stride[1] % 4) == 0;
-}
-
-static FastParams make_fast_params (const VideoPlan &p, bool rgb24 = false)
-{
-  FastParams fp;
-  fp.width = p.front.width;
-  fp.height = p.front.height;
-  fast_params_finish (fp, p.matrix.p, p.post.pack_pos, p.front.u_plane);
-  /* with a source crop the chroma upsampler still sees the frame's rows above / below the crop (do_unpack_lines :2966) */
-  fp.crow_lo = -(p.rect.in_y >> 1);
-  fp.crow_hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
-  if (rgb24)
-    fast_params_rgb24 (fp, p.matrix.p, p.fout->pos, p.front.u_plane);
-  return fp;
-}
-
 // rectangle complement of every destination plane <- the border pixel (convert_fill_border :7190-7290)
 static hipError_t fill_borders (const VideoPlan &p, uint8_t *const planes[4], const int strides[4], hipStream_t stream)
 {
@@ -493,9 +474,8 @@ static int build_tables (GstAmdVideoConverter *c)
       c->geom[i] = pass_tile_geom (p.passes[i]);
   {
     int lo, hi;
-    if (!tuning_on ("GSTAMD_NO_COL") && col_plan_regular (p, &lo, &hi) &&
-        col_choose (p.passes[0], p.passes[1], p.front.width, p.front.height, std::max (0, tuning_int ("GSTAMD_COL_OPL", 0)), tuning_int ("GSTAMD_COL_SHARE", 1) != 0,
-            &c->col, &c->col_form, !tuning_on ("GSTAMD_COL_NO_REGWIN"))) {
+    if (!tuning_on ("GSTAMD_NO_COL") && col_plan_ok (p, std::max (0, tuning_int ("GSTAMD_COL_OPL", 0)), tuning_int ("GSTAMD_COL_SHARE", 1) != 0,
+            !tuning_on ("GSTAMD_COL_NO_REGWIN"), &c->col, &c->col_form, &lo, &hi)) {
       c->reg_lo = lo;
       c->reg_hi = hi;
       if (col_pick_waves (c)) {
@@ -515,23 +495,8 @@ static int build_tables (GstAmdVideoConverter *c)
       }
     }
   }
-  if (p.passes.size () == 2 && p.passes[0].horizontal && p.passes[0].kind == SCALE_NTAP && p.passes[0].dot4_ok && c->geom[0].tile16_w > 0 &&
-      p.front.chroma_v2 == 1 && kind_has_planes (p.front.kind) && p.front.w_sub == 1 && p.front.h_sub == 1 && !p.matrix_before_scale &&
-      (int) p.vpair.size () >= 2 * p.front.height) {
-    /* k_hscale420_reg: is the planner's simulated pair table the closed form (every line consumed in order)? */
-    c->reg_lo = -(p.rect.in_y >> 1);
-    c->reg_hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
-    bool regular = true;
-    for (int y = 0; y < p.front.height && regular; y++) {
-      int heavy, light;
-      h420r_rows (c->reg_lo, c->reg_hi, y, &heavy, &light);
-      const int e0 = p.vpair[2 * y], ta = vpair_row (e0), tb = p.vpair[2 * y + 1];
-      const int th = vpair_role (e0) == 0 ? ta : tb, tl = vpair_role (e0) == 0 ? tb : ta;
-      regular = th == heavy && tl == light;
-    }
-    c->reg420 = regular;
-    if (regular && !p.passes[1].horizontal && p.passes[1].kind == SCALE_NTAP && p.passes[0].nw >= 3 && p.passes[0].nw <= 5 &&
-        !tuning_on ("GSTAMD_NO_FUSED420") && make_fused420_tables (p.passes[1], p.front.height, &c->fused) &&
+  if ((c->reg420 = hscale420_reg_plan_ok (p, c->geom[0], &c->reg_lo, &c->reg_hi))) {
+    if (!tuning_on ("GSTAMD_NO_FUSED420") && fused420_plan_ok (p, &c->fused) &&
         fused_pick_geometry (c, (p.passes[0].out_size + c->geom[0].tile16_w - 1) / c->geom[0].tile16_w)) {
       if ((e = hipMalloc ((void **) &c->vgroup_dev, c->fused.vgroup.size () * sizeof (int32_t))) != hipSuccess ||
           (e = hipMemcpy (c->vgroup_dev, c->fused.vgroup.data (), c->fused.vgroup.size () * sizeof (int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
@@ -710,6 +675,12 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
 static int convert_rect (GstAmdVideoConverter *c, const Planes &pl, void *const dest_planes[GSTAMD_VIDEO_MAX_PLANES],
     const int32_t dest_stride[GSTAMD_VIDEO_MAX_PLANES], hipStream_t stream);
 
+// pass i of the plan with its tables on the device
+static ScaleDev pass_scale_dev (const GstAmdVideoConverter *c, size_t i)
+{
+  return make_scale_dev (c->plan.passes[i], c->pass_dev[i].offset, c->pass_dev[i].taps, c->pass_dev[i].tapw);
+}
+
 // does this composite plan go through k_deep_scale_pack (video_deep_pack.h)?  *dp: everything but the pointers
 static bool deep_pack_usable (const GstAmdVideoConverter *c, DeepPackParams *dp)
 {
@@ -883,15 +854,9 @@ static int convert_gamma (GstAmdVideoConverter *c, const void *const src_planes[
       c->sub_out->deep_hook = nullptr;
       return r;
     }
-    if (n >= 1 && p.passes[0].horizontal && !dec16 && (mid_done || g.shrink) && front_hscale16_usable (p.front)) {
+    if (n >= 1 && p.passes[0].horizontal && !dec16 && (mid_done || g.shrink) && front_hscale16_usable (p.front, !tuning_on ("GSTAMD_NO_CONVERT16_FAST"))) {
       /* nothing between the front and a first, horizontal pass: the front runs inside it (k_front_hscale16), no full-size AYUV64 image */
-      ScaleDev sd;
-      memset (&sd, 0, sizeof (sd));
-      sd.kind = p.passes[0].kind;
-      sd.n_taps = p.passes[0].n_taps;
-      sd.inc = p.passes[0].inc;
-      sd.offset = c->pass_dev[0].offset;
-      sd.taps = c->pass_dev[0].taps;
+      const ScaleDev sd = pass_scale_dev (c, 0);
       const int ow = p.passes[0].out_size;
       if ((e = launch_front_hscale16 (p.front, pl, c->vpair_dev, sd, c->deep_b, ow * 8, ow, stream)) != hipSuccess)
         return hip_fail (e, "k_front_hscale16");
@@ -945,16 +910,7 @@ static int convert_gamma (GstAmdVideoConverter *c, const void *const src_planes[
       mid_done = true;
     }
     for (size_t i = first_pass; i < n; i++) {
-      ScaleDev sd;
-      memset (&sd, 0, sizeof (sd));
-      sd.kind = p.passes[i].kind;
-      sd.n_taps = p.passes[i].n_taps;
-      sd.inc = p.passes[i].inc;
-      sd.offset = c->pass_dev[i].offset;
-      sd.taps = c->pass_dev[i].taps;
-      sd.tapw = c->pass_dev[i].tapw;
-      sd.nw = p.passes[i].nw;
-      sd.nw4 = p.passes[i].nw4;
+      const ScaleDev sd = pass_scale_dev (c, i);
       const bool hz = p.passes[i].horizontal;
       const int ow = hz ? p.passes[i].out_size : cur.width, oh = hz ? cur.height : p.passes[i].out_size;
       uint8_t *dst = cur.p == c->deep_a ? c->deep_b : c->deep_a;
@@ -1400,26 +1356,14 @@ static int convert_rect (GstAmdVideoConverter *c, const Planes &pl, void *const 
   return convert_to_packed (c, pl, (uint8_t *) dest_planes[0], dest_stride ? dest_stride[0] : p.out_info.stride[0], stream);
 }
 
-// Does the plan take the direct 4:2:0 bilinear kernels (video_bilinear_fast.h / video_bilinear_rows.h)?  Fills everything of
-// BilParams that does not depend on a particular frame's pointers.
-// k_scale_col applies to these planes: the plan's tables exist, no colour step ahead of the scaler, U and V planes of one pitch
-static bool col_usable (const GstAmdVideoConverter *c, const Planes &pl, const ColorParams &pre)
-{
-  const VideoPlan &p = c->plan;
-  return c->col_ok && pre.matrix.kind == MATRIX_NONE && pre.alpha_kind == ALPHA_NONE &&
-      (p.front.kind == UNPACK_SEMI || pl.stride[p.front.u_plane] == pl.stride[p.front.v_plane]);
-}
-
 // one frame, or the armed frame list behind it (video_kernels.hip) when every destination of it is aligned like this one: launches of up to
 // GSTAMD_COL_MAX_FRAMES frames
 static hipError_t col_launch (GstAmdVideoConverter *c, const Planes &pl, uint8_t *dst, int dstride, const ColorParams &post, const PostFast &pf, hipStream_t stream)
 {
   const VideoPlan &p = c->plan;
   const bool semi = p.front.kind == UNPACK_SEMI;
-  /* the destination rows launch_scale_col refuses, decided before the list is taken (col_ok: the kernel form, its waves and LDS fit) */
+  /* col_dst_ok said yes for this frame (col_ok: the kernel form, its waves and LDS fit); the list's other frames have to sit on the same unit */
   const int unit = 4 * c->col_form.opl;
-  if ((dstride % unit) != 0 || ((uintptr_t) dst % unit) != 0)
-    return hipErrorNotSupported;
   int n;
   const FrameDeltas &fl = video_frame_list_peek (pl.p[0], dst, &n);
   for (int f = 1; f < n; f++)
@@ -1429,21 +1373,7 @@ static hipError_t col_launch (GstAmdVideoConverter *c, const Planes &pl, uint8_t
     (void) video_frame_list_for (pl.p[0], dst, &n, GSTAMD_COL_MAX_FRAMES);
   else
     video_frame_list_touch (dst);
-  ColParams q;
-  memset ((void *) &q, 0, sizeof (q));
-  q.ystride = pl.stride[0];
-  q.cstride = semi ? pl.stride[1] : pl.stride[p.front.u_plane];
-  q.width = p.front.width;
-  q.height = p.front.height;
-  q.u_first = p.front.u_plane != 0;
-  q.crow_lo = c->reg_lo;
-  q.crow_hi = c->reg_hi;
-  q.tiles = c->col_tiles_dev;
-  q.hout = c->col_hout_dev;
-  q.vrow = c->col_vrow_dev;
-  q.out_w = p.passes[0].out_size;
-  q.out_h = p.passes[1].out_size;
-  q.dstride = dstride;
+  ColParams q = make_col_params (p, pl, c->reg_lo, c->reg_hi, c->col_tiles_dev, c->col_hout_dev, c->col_vrow_dev, dstride);
   for (int base = 0; base < n; base += GSTAMD_COL_MAX_FRAMES) {
     const int nb = std::min (n - base, GSTAMD_COL_MAX_FRAMES);
     col_geometry (c, nb, &q);
@@ -1491,81 +1421,20 @@ static hipError_t col_launch (GstAmdVideoConverter *c, const Planes &pl, uint8_t
   return hipSuccess;
 }
 
-static bool bilinear420_params (GstAmdVideoConverter *c, BilParams *out)
+// the plan's answer for the 4:2:0 bilinear kernels (bilinear420_params of video_dispatch.h) under the library's knobs
+static bool bilinear420_plan (const GstAmdVideoConverter *c, BilParams *bp)
 {
-  const VideoPlan &p = c->plan;
-  const auto small_kind = [](int k) { return k == SCALE_NEAREST || k == SCALE_2TAP; };
-  /* no colour stage at all (YUV -> YUV of one colorimetry: the pack image of a planar / semi-planar destination, an AYUV frame): the same kernels
-     with the layout that stores A Y U V (GSTAMD_LAYOUT_AYUV) - NV12 4K -> I420 1080p took 65 us through the generic wave-tile scaler */
-  const bool ayuv = bilinear420_ayuv_plan (p) && !tuning_on ("GSTAMD_NO_BILINEAR_AYUV");
-  if ((p.out_planar && !ayuv) || p.passes.size () != 2 || !small_kind (p.passes[0].kind) || !small_kind (p.passes[1].kind))
-    return false;
-  /* semi-planar / planar 4:2:0 source, horizontal-first 2-tap x 2-tap, fast matrix */
-  if (!(p.passes[0].horizontal && p.passes[0].kind == SCALE_2TAP && p.passes[1].kind == SCALE_2TAP && kind_has_planes (p.front.kind) && p.front.w_sub == 1 &&
-        p.front.h_sub == 1 && !p.matrix_before_scale && (p.fast_post || ayuv) && p.front.chroma_v2 != 2 && !tuning_on ("GSTAMD_NO_BILINEAR420")))
-    return false;
-  const int out_w = p.out_info.width, out_h = p.out_info.height;
-  BilParams bp;
-  memset (&bp, 0, sizeof (bp));
-  bp.tile_w = bil_pick_tile (out_w, p.passes[0].inc, &bp.ylen);
-  if (tuning_on ("GSTAMD_BIL_TILE")) {      /* tuning knob for profiling sessions */
-    bp.tile_w = tuning_int ("GSTAMD_BIL_TILE", 0);
-    bp.ylen = bil_ylen (out_w, p.passes[0].inc, bp.tile_w);
-  }
-  if (bp.tile_w <= 0 || bp.ylen <= 0)
-    return false;
-  bp.fp = make_fast_params (p);
-  bp.fp.ayuv = ayuv ? (p.matrix.kind == MATRIX_NONE ? 1 : 2) : 0;
-  bp.fp.m8 = p.matrix;
-  bp.out_w = out_w;
-  bp.out_h = out_h;
-  bp.inc = p.passes[0].inc;
-  bp.voffset = c->pass_dev[1].offset;
-  bp.vtaps = c->pass_dev[1].taps;
-  bp.vpair = p.front.chroma_v2 ? c->vpair_dev : nullptr;
-  bp.regular_pairs = 0;
-  bp.planar = p.front.kind == UNPACK_PLANAR;
-  bp.u_plane = p.front.u_plane;
-  bp.v_plane = p.front.v_plane;
-  if (p.front.chroma_v2 && !tuning_on ("GSTAMD_BIL_TABLE")) {
-    /* are the pairs of every source line the kernel will touch the closed form of bil_rows? */
-    bool regular = true;
-    BilParams probe = bp;
-    probe.regular_pairs = 1;
-    for (int y = 0; y < out_h && regular; y++)
-      for (int l = 0; l < 2 && regular; l++) {
-        const int line = (int) p.passes[1].offset[y] + l;
-        int ra, rb, role;
-        bil_rows (probe, line, &ra, &rb, &role);
-        const int e0 = p.vpair[2 * line], ta = vpair_row (e0), trole = vpair_role (e0), tb = p.vpair[2 * line + 1];
-        regular = ta == ra && tb == rb && (ra == rb || trole == role);
-      }
-    bp.regular_pairs = regular ? 1 : 0;
-  }
-  /* rows per wave of k_bilinear420_rows: every source line pair has to sit in the three-row window of video_bilinear_rows.h */
-  bp.rows = 0;
-  if (bp.regular_pairs && (p.front.width % 16) == 0 && !tuning_on ("GSTAMD_NO_BILINEAR_ROWS")) {
-    bool fits = true;
-    for (int y = 0; y < out_h && fits; y++)
-      fits = bilr_window_matches (bp, (int) p.passes[1].offset[y]);
-    int rows_ylen = 0;
-    bp.rows_tile_w = bilr_pick_tile (out_w, p.passes[0].inc, &rows_ylen);
+  BilKnobs k = {!tuning_on ("GSTAMD_NO_BILINEAR420"), !tuning_on ("GSTAMD_NO_BILINEAR_AYUV"), tuning_on ("GSTAMD_BIL_TABLE"), !tuning_on ("GSTAMD_NO_BILINEAR_ROWS"),
+    !tuning_on ("GSTAMD_NO_BILINEAR_HALF"), tuning_int ("GSTAMD_BIL_TILE", -1), -1};      /* (BIL_TILE: tuning knob for profiling sessions) */
 #ifdef GSTAMD_TUNING
-    if (tuning_on ("GSTAMD_BIL_ROWS_TILE")) {
-      bp.rows_tile_w = tuning_int ("GSTAMD_BIL_ROWS_TILE", 0);
-      rows_ylen = bil_ylen (out_w, p.passes[0].inc, bp.rows_tile_w);
-    }
+  k.rows_tile = tuning_int ("GSTAMD_BIL_ROWS_TILE", -1);
 #endif
-    fits = fits && bp.rows_tile_w > 0 && rows_ylen > 0;
-    if (fits)
-      bp.rows = -1;
+  if (!bilinear420_params (c->plan, k, c->pass_dev[1].offset, c->pass_dev[1].taps, c->vpair_dev, bp))
+    return false;
 #ifdef GSTAMD_TUNING
-    if (fits && tuning_on ("GSTAMD_BIL_ROWS"))
-      bp.rows = tuning_int ("GSTAMD_BIL_ROWS", 0);
+  if (bp->rows != 0 && tuning_on ("GSTAMD_BIL_ROWS"))
+    bp->rows = tuning_int ("GSTAMD_BIL_ROWS", 0);
 #endif
-  }
-  bp.half = !tuning_on ("GSTAMD_NO_BILINEAR_HALF") && bilh_plan_ok (bp, p.passes[1].offset.data (), p.passes[1].taps.data ());
-  *out = bp;
   return true;
 }
 
@@ -1575,7 +1444,7 @@ static bool bilinear420_params (GstAmdVideoConverter *c, BilParams *out)
 static int convert_deep_scaled (GstAmdVideoConverter *c, const Planes &pl, uint8_t *dst, int dstride, hipStream_t stream)
 {
   const VideoPlan &p = c->plan;
-  const int in_w = p.front.width, in_h = p.front.height, out_w = p.out_info.width, out_h = p.out_info.height;
+  const int in_w = p.front.width, in_h = p.front.height;
   const size_t n = p.passes.size ();
   const size_t bpp = p.matrix_before_scale ? 4 : 8;
   DeepPackParams ds4;
@@ -1610,21 +1479,12 @@ static int convert_deep_scaled (GstAmdVideoConverter *c, const Planes &pl, uint8
     c->deep_b_size = need_b;
   }
   ScaleDev sd[2];
-  for (size_t i = 0; i < n; i++) {
-    memset (&sd[i], 0, sizeof (sd[i]));
-    sd[i].kind = p.passes[i].kind;
-    sd[i].n_taps = p.passes[i].n_taps;
-    sd[i].inc = p.passes[i].inc;
-    sd[i].offset = c->pass_dev[i].offset;
-    sd[i].taps = c->pass_dev[i].taps;
-    sd[i].tapw = c->pass_dev[i].tapw;
-    sd[i].nw = p.passes[i].nw;
-    sd[i].nw4 = p.passes[i].nw4;
-  }
+  for (size_t i = 0; i < n; i++)
+    sd[i] = pass_scale_dev (c, i);
   if (!p.matrix_before_scale) {
     Deep16Image cur = {c->deep_a, in_w * 8, in_w, in_h};
     size_t first = 0;
-    if (n == 2 && p.passes[0].horizontal && front_hscale16_usable (p.front)) {
+    if (n == 2 && p.passes[0].horizontal && front_hscale16_usable (p.front, !tuning_on ("GSTAMD_NO_CONVERT16_FAST"))) {
       /* the front inside the first, horizontal pass: no full-size AYUV64 image */
       if ((e = launch_front_hscale16 (p.front, pl, c->vpair_dev, sd[0], c->deep_b, mid_w * 8, mid_w, stream)) != hipSuccess)
         return hip_fail (e, "k_front_hscale16");
@@ -1666,8 +1526,6 @@ static int convert_deep_scaled (GstAmdVideoConverter *c, const Planes &pl, uint8
       return hip_fail (e, "scale pass (8-bit lines of a 10-bit source)");
     src = c->deep_b, sw = ow, sh = oh;
   }
-  (void) out_w;
-  (void) out_h;
   return GSTAMD_OK;
 }
 
@@ -1690,51 +1548,26 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
     e = launch_convert_pair (fp, p.front.chroma_h, pl.p[0], pl.p[1], dst, pl.stride[0], pl.stride[1], dstride, stream);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert_pair");
   }
-  if (p.fast_420p && ((uintptr_t) pl.p[0] % 8) == 0 && (pl.stride[0] % 8) == 0 && ((uintptr_t) pl.p[1] % 4) == 0 && ((uintptr_t) pl.p[2] % 4) == 0 &&
-      (pl.stride[1] % 4) == 0 && pl.stride[1] == pl.stride[2] && ((uintptr_t) dst % 16) == 0 && (dstride % 16) == 0 &&
-      !tuning_on ("GSTAMD_NO_FAST420P")) {
-    Fast420pParams q;
-    q.fp = make_fast_params (p);
-    q.y = pl.p[0];
-    q.u = pl.p[p.front.u_plane];
-    q.v = pl.p[p.front.v_plane];
-    q.ystride = pl.stride[0];
-    q.cstride = pl.stride[1];
-    e = launch_convert420p (q, dst, dstride, stream);
+  if (convert420p_usable (p, pl, dst, dstride) && !tuning_on ("GSTAMD_NO_FAST420P")) {
+    e = launch_convert420p (make_fast420p_params (p, pl), dst, dstride, stream);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert420p");
   }
-  if (p.fast_422 && ((uintptr_t) pl.p[0] % 16) == 0 && (pl.stride[0] % 16) == 0 && ((uintptr_t) dst % 16) == 0 && (dstride % 16) == 0 &&
-      !tuning_on ("GSTAMD_NO_FAST422")) {
-    Fast422Params q;
-    q.fp = make_fast_params (p);
-    q.chroma_h = p.front.chroma_h;
-    fast422_selectors (p.front.pos[1], p.front.pos[2], p.front.pos[3], &q);
-    e = launch_convert422 (q, pl.p[0], pl.stride[0], dst, dstride, stream);
+  if (convert422_usable (p, false, pl, dst, dstride) && !tuning_on ("GSTAMD_NO_FAST422")) {
+    e = launch_convert422 (make_fast422_params (p, false), pl.p[0], pl.stride[0], dst, dstride, stream);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert422");
   }
-  if (p.fast_422_ayuv && !c->hook_on && ((uintptr_t) pl.p[0] % 16) == 0 && (pl.stride[0] % 16) == 0 && ((uintptr_t) dst % 16) == 0 && (dstride % 16) == 0 &&
-      !tuning_on ("GSTAMD_NO_FAST422")) {
-    Fast422Params q;
-    memset ((void *) &q, 0, sizeof (q));
-    q.fp.width = p.front.width;
-    q.fp.height = p.front.height;
-    q.chroma_h = p.front.chroma_h;
-    fast422_selectors (p.front.pos[1], p.front.pos[2], p.front.pos[3], &q);
-    e = launch_convert422 (q, pl.p[0], pl.stride[0], dst, dstride, stream, true);
+  if (!c->hook_on && convert422_usable (p, true, pl, dst, dstride) && !tuning_on ("GSTAMD_NO_FAST422")) {
+    e = launch_convert422 (make_fast422_params (p, true), pl.p[0], pl.stride[0], dst, dstride, stream, true);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert422_ayuv");
   }
   if (p.deep16) {
-    /* (the byte-stream kinds - NV12_10LE40 & co, UYVP - are read byte by byte: rows of five-byte groups have no alignment; the three-samples-per-word
-       kinds are read as 32-bit words) */
-    const bool bytes_in = p.front.kind == UNPACK_SEMI_LE40 || p.front.kind == UNPACK_P422_UYVP || p.front.kind == UNPACK_SEMI_LE40_TILED;
-    const bool words_in = p.front.kind == UNPACK_SEMI_LE32 || p.front.kind == UNPACK_GRAY_LE32;
-    if (words_in && (((uintptr_t) pl.p[0] % 4) != 0 || (pl.stride[0] % 4) != 0 || (p.front.kind == UNPACK_SEMI_LE32 && (((uintptr_t) pl.p[1] % 4) != 0 || (pl.stride[1] % 4) != 0))))
-      return set_error (GSTAMD_ERR_UNSUPPORTED, "frames with three 10-bit samples per 32-bit word need 4-byte aligned planes and pitches");
-    if (((uintptr_t) dst % 4) != 0 || (dstride % 4) != 0)
-      return set_error (GSTAMD_ERR_UNSUPPORTED, "10-bit frames need 2-byte aligned planes and pitches, the destination 4-byte aligned ones");
-    if (!bytes_in && (((uintptr_t) pl.p[0] % 2) != 0 || (pl.stride[0] % 2) != 0 || ((uintptr_t) pl.p[1] % 2) != 0 ||
-        (pl.stride[1] % 2) != 0 || (p.front.kind == UNPACK_PLANAR && (((uintptr_t) pl.p[2] % 2) != 0 || (pl.stride[2] % 2) != 0))))
-      return set_error (GSTAMD_ERR_UNSUPPORTED, "10-bit frames need 2-byte aligned planes and pitches, the destination 4-byte aligned ones");
+    switch (deep16_refusal (p, pl, dst, dstride)) {
+      case 1:
+        return set_error (GSTAMD_ERR_UNSUPPORTED, "frames with three 10-bit samples per 32-bit word need 4-byte aligned planes and pitches");
+      case 2:
+      case 3:
+        return set_error (GSTAMD_ERR_UNSUPPORTED, "10-bit frames need 2-byte aligned planes and pitches, the destination 4-byte aligned ones");
+    }
     if (p.passes.empty ()) {
       e = launch_convert16 (p.front, pl, c->vpair_dev, p.deep, p.post, dst, dstride, stream);
       return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert16");
@@ -1746,13 +1579,10 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
       e = launch_convert_gamma (p.front, pl, c->vpair_dev, color, p.post.pack_pos, dst, dstride, c->hook, stream);
       return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_convert_gamma");
     }
-    if (p.front.kind == UNPACK_PACKED3 && p.front.hi_depth == 0 && color.matrix.kind == MATRIX_NONE && color.alpha_kind == ALPHA_NONE &&
-        !tuning_on ("GSTAMD_NO_SWIZZLE34")) {
-      Swz34Params sp;
-      if (swizzle34_setup (3, p.front.pos, 4, p.post.pack_pos, pl.p[0], pl.stride[0], dst, dstride, p.front.width, &sp)) {
-        e = launch_swizzle34 (sp, 3, 4, p.front.height, stream);
-        return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_swizzle34");
-      }
+    Swz34Params sp;
+    if (!tuning_on ("GSTAMD_NO_SWIZZLE34") && swizzle34_usable (p, color, pl, dst, dstride, &sp)) {
+      e = launch_swizzle34 (sp, 3, 4, p.front.height, stream);
+      return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_swizzle34");
     }
     if (swizzle4_usable (p.front, pl, color, dst, dstride)) {
       e = launch_swizzle4 (p.front, pl, p.post.pack_pos, dst, dstride, stream);
@@ -1765,30 +1595,20 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
   const ColorParams &pre = p.matrix_before_scale ? color : none;
   const ColorParams &post = p.matrix_before_scale ? none : color;
   ScaleDev sd[2];
-  for (size_t i = 0; i < p.passes.size (); i++) {
-    sd[i].kind = p.passes[i].kind;
-    sd[i].n_taps = p.passes[i].n_taps;
-    sd[i].inc = p.passes[i].inc;
-    sd[i].offset = c->pass_dev[i].offset;
-    sd[i].taps = c->pass_dev[i].taps;
-    sd[i].tapw = c->pass_dev[i].tapw;
-    sd[i].nw = p.passes[i].nw;
-    sd[i].nw4 = p.passes[i].nw4;
-  }
+  for (size_t i = 0; i < p.passes.size (); i++)
+    sd[i] = pass_scale_dev (c, i);
   const int out_w = p.out_info.width, out_h = p.out_info.height;
   PostFast pf, pf_none;
   memset (&pf_none, 0, sizeof (pf_none));
   pf.use = p.fast_post ? 1 : 0;
   pf.fp = make_fast_params (p);
-  const auto small_kind = [](int k) { return k == SCALE_NEAREST || k == SCALE_2TAP; };
-  if (p.passes.size () == 2 && small_kind (p.passes[0].kind) && small_kind (p.passes[1].kind)) {
+  if (bilinear_plan (p)) {
     /* nearest / 2-tap in both directions ("bilinear"): one fused kernel, no intermediate image */
     const bool h_first = p.passes[0].horizontal;
     BilParams bp;
-    if (((uintptr_t) dst % 4) == 0 && (dstride % 4) == 0 && bilinear420_params (c, &bp)) {
+    if (rows_aligned (dst, dstride, 4) && bilinear420_plan (c, &bp) && bilinear420_usable (bp, pl, dst, dstride)) {
       e = launch_bilinear420 (bp, p.front.chroma_h, pl, dst, dstride, stream);
-      if (e != hipErrorNotSupported)
-        return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_bilinear420");
+      return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_bilinear420");
     }
     const ScaleDev &sh = h_first ? sd[0] : sd[1], &sv = h_first ? sd[1] : sd[0];
     if (c->raw4_quad && pl.p[0] && !tuning_on ("GSTAMD_NO_PLANE_QUAD")) {
@@ -1810,11 +1630,9 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
       e = launch_plane_frame (jobs, 0, stream);
       return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_plane_quad(4-byte pixels)");
     }
-    if (p.matrix_before_scale && p.front.kind != UNPACK_PACKED4 && p.front.hi_depth == 0 && ((uintptr_t) dst % 4) == 0 && (dstride % 4) == 0 &&
-        !tuning_on ("GSTAMD_NO_BILINEAR4")) {
-      /* enlarging (the matrix runs on the source's pixels, chain_convert ahead of chain_scale): the source frame through the front and the
-         colour stage into an A, c1, c2, c3 image of ITS size - one of the unscaled kernels, a quarter of the destination's pixels at 1080p
-         -> 4K - and the four-outputs-per-lane scaler from that image; the scaler works per byte, so this is the chain's own order */
+    if (bilinear4_pre_usable (p, dst, dstride) && !tuning_on ("GSTAMD_NO_BILINEAR4")) {
+      /* the image of the source's size comes from one of the unscaled kernels - a quarter of the destination's pixels at 1080p -> 4K - and the
+         four-outputs-per-lane scaler reads it; the scaler works per byte, so this is the chain's own order */
       const int in_w = p.front.width, in_h = p.front.height;
       const size_t need = (size_t) in_w * 4 * in_h;
       if (c->pre_img_size < need) {
@@ -1827,16 +1645,9 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
         c->pre_img_size = need;
       }
       const int ident[4] = {0, 1, 2, 3};
-      if (p.fast_pre && ((uintptr_t) pl.p[0] % 4) == 0 && (pl.stride[0] % 4) == 0 && ((uintptr_t) pl.p[1] % 4) == 0 && (pl.stride[1] % 4) == 0 &&
-          !tuning_on ("GSTAMD_NO_FAST_PRE")) {
-        /* NV12 / NV21: that image is the unscaled conversion into A, R, G, B bytes - the line-pair kernel (11 MB at 1080p: 13 us through the per-pixel
-           kernel, round 6) */
-        FastParams fp;
-        fp.width = in_w, fp.height = in_h;
-        fast_params_finish (fp, p.matrix.p, ident, p.front.u_plane);
-        fp.crow_lo = -(p.rect.in_y >> 1);
-        fp.crow_hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
-        if ((e = launch_convert_pair (fp, p.front.chroma_h, pl.p[0], pl.p[1], c->pre_img, pl.stride[0], pl.stride[1], in_w * 4, stream)) != hipSuccess)
+      if (fast_pre_usable (p, pl) && !tuning_on ("GSTAMD_NO_FAST_PRE")) {
+        /* (11 MB at 1080p: 13 us through the per-pixel kernel, round 6) */
+        if ((e = launch_convert_pair (make_fast_pre_params (p), p.front.chroma_h, pl.p[0], pl.p[1], c->pre_img, pl.stride[0], pl.stride[1], in_w * 4, stream)) != hipSuccess)
           return hip_fail (e, "k_convert_pair(source size)");
       } else
       if ((e = launch_convert (p.front, pl, c->vpair_dev, pre, ident, c->pre_img, in_w * 4, stream, 0)) != hipSuccess)
@@ -1859,11 +1670,7 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
         out_w, out_h, p.passes[h_first ? 0 : 1].max_span, c->geom[h_first ? 0 : 1], pf, stream);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "k_scale2x2");
   }
-  /* a 4-byte packed source whose unpack is the identity (ARGB, AYUV, and every 4-byte format in plane scaling, where the bytes go through
-     raw) with no colour step before the scaler IS an image in the scalers' own layout: the image kernels (wave tiles, k_vscale_pk) take it
-     directly instead of the one-lane-per-pixel front kernels */
-  const bool raw4 = p.front.kind == UNPACK_PACKED4 && p.front.pos[0] == 0 && p.front.pos[1] == 1 && p.front.pos[2] == 2 && p.front.pos[3] == 3 &&
-      pre.matrix.kind == MATRIX_NONE && pre.alpha_kind == ALPHA_NONE && ((uintptr_t) pl.p[0] % 4) == 0 && (pl.stride[0] % 4) == 0;
+  const bool raw4 = raw4_source (p, pre, pl);
   if (p.passes.size () == 1) {
     if (raw4)
       e = launch_scale_from_image (p.passes[0].horizontal, pl.p[0], pl.stride[0], sd[0], dst, dstride, true, post, p.post.pack_pos, out_w, out_h,
@@ -1873,36 +1680,22 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
         post, p.post.pack_pos, out_w, out_h, p.passes[0].max_span, c->geom[0], pf, stream);
     return e == hipSuccess ? GSTAMD_OK : hip_fail (e, "scale pass");
   }
-  if (col_usable (c, pl, pre)) {
+  /* The launchers below may still answer hipErrorNotSupported behind their gates - launch_scale_col and launch_scale420_fused where the LDS or
+     the waves the form needs do not fit this device - so these rungs fall through to the next one rather than guess what the device says */
+  const bool regular420 = regular420_frame_ok (p, pl, pre);
+  if (c->col_ok && regular420 && col_dst_ok (c->col_form, dst, dstride)) {
     e = col_launch (c, pl, dst, dstride, post, pf, stream);
     if (e == hipSuccess)
       return GSTAMD_OK;
     if (e != hipErrorNotSupported)
       return hip_fail (e, "k_scale_col");
   }
-  e = hipErrorNotSupported;
-  const bool reg_usable = c->reg420 && pre.matrix.kind == MATRIX_NONE && pre.alpha_kind == ALPHA_NONE &&
-      (p.front.kind == UNPACK_SEMI || pl.stride[p.front.u_plane] == pl.stride[p.front.v_plane]);
-  if (reg_usable && c->fused_ok) {
+  const bool reg_usable = c->reg420 && regular420;
+  H420RegParams hp = reg_usable ? make_h420_reg_params (p, pl, c->reg_lo, c->reg_hi, sd[0], c->geom[0].tile16_w, nullptr, 0) : H420RegParams ();
+  if (reg_usable && c->fused_ok && hscale420_reg_frame_ok (hp, sd[0].nw, dst, dstride)) {
     Fused420Params fq;
     memset (&fq, 0, sizeof (fq));
-    H420RegParams &hp = fq.h;
-    hp.y = pl.p[0];
-    hp.ystride = pl.stride[0];
-    hp.semi = p.front.kind == UNPACK_SEMI;
-    hp.u_first = p.front.u_plane != 0;
-    hp.c0 = hp.semi ? pl.p[1] : pl.p[p.front.u_plane];
-    hp.c1 = hp.semi ? pl.p[1] : pl.p[p.front.v_plane];
-    hp.cstride = hp.semi ? pl.stride[1] : pl.stride[p.front.u_plane];
-    hp.width = p.front.width;
-    hp.height = p.front.height;
-    hp.crow_lo = c->reg_lo;
-    hp.crow_hi = c->reg_hi;
-    hp.offset = sd[0].offset;
-    hp.tapw = sd[0].tapw;
-    hp.nw4 = sd[0].nw4;
-    hp.out_w = p.passes[0].out_size;
-    hp.tile_w = c->geom[0].tile16_w;
+    fq.h = hp;
     fq.n_taps_h = sd[0].n_taps;
     fq.vgroup = c->vgroup_dev;
     fq.vtapw = c->vtapw_dev;
@@ -1920,7 +1713,6 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
     if (trace_path && hipMalloc ((void **) &fq.trace, trace_n * 8) == hipSuccess)
       (void) hipMemset (fq.trace, 0, trace_n * 8);
 #endif
-    e = hipErrorNotSupported;
     e = launch_scale420_fused (fq, p.front.chroma_h, sd[0].nw, c->fused_waves, dst, dstride, post, p.post.pack_pos, pf, stream);
 #ifdef GSTAMD_TUNING
     if (fq.trace) {
@@ -1942,27 +1734,8 @@ static int convert_to_packed (GstAmdVideoConverter *c, const Planes &pl, uint8_t
   if (!c->tmp && (e = hipMalloc ((void **) &c->tmp, c->tmp_size)) != hipSuccess)
     return hip_fail (e, "hipMalloc(tmp)");
   e = hipErrorNotSupported;
-  if (reg_usable) {
-    H420RegParams hp;
-    memset (&hp, 0, sizeof (hp));
-    hp.y = pl.p[0];
-    hp.ystride = pl.stride[0];
-    hp.semi = p.front.kind == UNPACK_SEMI;
-    hp.u_first = p.front.u_plane != 0;
-    hp.c0 = hp.semi ? pl.p[1] : pl.p[p.front.u_plane];
-    hp.c1 = hp.semi ? pl.p[1] : pl.p[p.front.v_plane];
-    hp.cstride = hp.semi ? pl.stride[1] : pl.stride[p.front.u_plane];
-    hp.width = p.front.width;
-    hp.height = p.front.height;
-    hp.crow_lo = c->reg_lo;
-    hp.crow_hi = c->reg_hi;
-    hp.offset = sd[0].offset;
-    hp.tapw = sd[0].tapw;
-    hp.nw4 = sd[0].nw4;
-    hp.dst = c->tmp;
-    hp.dstride = c->tmp_w * 4;
-    hp.out_w = c->tmp_w;
-    hp.tile_w = c->geom[0].tile16_w;
+  hp.dst = c->tmp, hp.dstride = c->tmp_w * 4;
+  if (reg_usable && !tuning_on ("GSTAMD_NO_H420_REG") && hscale420_reg_frame_ok (hp, sd[0].nw, hp.dst, hp.dstride)) {
     e = launch_hscale420_reg (hp, p.front.chroma_h, sd[0].nw, sd[0].n_taps, stream);
     if (e != hipSuccess && e != hipErrorNotSupported)
       return hip_fail (e, "k_hscale420_reg");

@@ -12,6 +12,7 @@
 #include "video_scale_fast.h"
 #include "video_hscale420.h"
 #include "video_scale420_fused.h"
+#include "video_dispatch.h"
 
 namespace gstamd {
 
@@ -230,8 +231,6 @@ __global__ __launch_bounds__ (1024) void k_scale420_fused2 (Fused420Params p, Ds
   }
 }
 
-static inline bool aligned (const void *p, size_t a) { return ((uintptr_t) p & (a - 1)) == 0; }
-
 template <int NW, int CH, int SEMI>
 static hipError_t launch_fused_ngv (const Fused420Params &p, const Dst &d, const PostFast &pf, int nwaves, size_t lds, dim3 grid, hipStream_t stream)
 {
@@ -275,13 +274,8 @@ hipError_t launch_scale420_fused (const Fused420Params &p, int chroma_h, int nw,
     const int pack_pos[4], const PostFast &pf, hipStream_t stream)
 {
   video_frame_list_touch (dst);
-  int ok = (p.h.width % 16) == 0 && aligned (p.h.y, 16) && (p.h.ystride % 16) == 0 && aligned (dst, 4) && (dstride % 4) == 0;
-  if (p.h.semi)
-    ok = ok && aligned (p.h.c0, 16) && (p.h.cstride % 16) == 0;
-  else
-    ok = ok && aligned (p.h.c0, 8) && aligned (p.h.c1, 8) && (p.h.cstride % 8) == 0;
   const size_t lds = fused420_lds_bytes (p.ring, nwaves, p.sched);
-  if (!ok || nw < 3 || nw > 5 || nwaves < 1 || nwaves > 16 || lds > 160 * 1024)
+  if (!hscale420_reg_frame_ok (p.h, nw, dst, dstride) || nwaves < 1 || nwaves > 16 || lds > 160 * 1024)
     return hipErrorNotSupported;
   Dst d;
   d.p = dst;

@@ -32,8 +32,6 @@ const FrameDeltas &video_frame_list_peek (const void *sp, const void *dp, int *n
 hipError_t launch_convert (const FrontParams &f, const Planes &pl, const int *vpair_dev, const ColorParams &color,
     const int pack_pos[4], uint8_t *dst, int dstride, hipStream_t stream, int extra_rows = 0);
 
-// 4-byte packed -> 4-byte packed, no matrix, no alpha operation: the copy-shaped permutation kernel
-bool swizzle4_usable (const FrontParams &f, const Planes &pl, const ColorParams &color, const uint8_t *dst, int dstride);
 hipError_t launch_swizzle4 (const FrontParams &f, const Planes &pl, const int pack_pos[4], uint8_t *dst, int dstride, hipStream_t stream);
 
 hipError_t launch_convert16 (const FrontParams &f, const Planes &pl, const int *vpair_dev, const Deep16Params &d, const PostParams &post, uint8_t *dst,
@@ -57,7 +55,6 @@ hipError_t launch_pack16_ed (const PackPlanarParams &pk, int hi_depth, const Dit
 hipError_t launch_dither16_image (const DitherParams &d, uint8_t *img, int stride, int w, int h, hipStream_t stream);
 struct Deep16Image;
 hipError_t launch_front16 (const FrontParams &f, const Planes &pl, const int *vpair_dev, uint8_t *img, int istride, hipStream_t stream);
-bool front_hscale16_usable (const FrontParams &f);
 hipError_t launch_front_hscale16 (const FrontParams &f, const Planes &pl, const int *vpair_dev, const ScaleDev &sd, uint8_t *dst, int dstride, int ow, hipStream_t stream);
 // d / post non-NULL: the last pass, fused with matrix16 + narrowing + alpha + pack into the 4-byte destination
 hipError_t launch_scale16 (const Deep16Image &im, const ScaleDev &sd, bool horizontal, uint8_t *dst, int dstride, int ow, int oh, const Deep16Params *d,
@@ -85,8 +82,7 @@ hipError_t launch_convert422 (const Fast422Params &p, const uint8_t *src, int ss
 hipError_t launch_convert420p (const Fast420pParams &p, uint8_t *dst, int dstride, hipStream_t stream);
 // one frame, or the armed frame list behind it in one launch when k_bilinear420_half / k_bilinear420_rows take every frame of it
 hipError_t launch_bilinear420 (const BilParams &bp, int chroma_h, const Planes &pl, uint8_t *dst, int dstride, hipStream_t stream);
-// the exact halving (BilParams::half) on frames whose rows are 16-byte aligned: video_bilinear_half.hip
-bool bilinear420_half_usable (const BilParams &bp, int n, const Planes *pl, uint8_t *const *dst, int dstride);
+// the exact halving (BilParams::half) on the frames bilinear420_half_usable takes: video_bilinear_half.hip
 hipError_t launch_bilinear420_half (const BilParams &bp, int chroma_h, int n, const Planes *pl, uint8_t *const *dst, int dstride, hipStream_t stream);
 hipError_t launch_plane_simple (int kind, const uint8_t *src, int sstride, uint8_t *dst, int dstride, int n_elems, int ow, int oh, hipStream_t stream);
 hipError_t launch_plane_pass (bool horizontal, const ScaleDev &sd, const uint8_t *src, int sstride, uint8_t *dst, int dstride, int n_elems,
@@ -97,8 +93,6 @@ struct Enc420Params;
 hipError_t launch_encode420 (const Enc420Params &ep, bool semi, const uint8_t *src, int sstride, uint8_t *const planes[3], const int strides[3],
     hipStream_t stream);
 hipError_t launch_plane_frame (const PlaneJobs &jobs, size_t lds_bytes, hipStream_t stream);
-bool swizzle34_setup (int src_bytes, const int *src_pos, int dst_bytes, const int *dst_pos, const uint8_t *src, int sstride, uint8_t *dst, int dstride,
-    int width, Swz34Params *p);
 hipError_t launch_swizzle34 (const Swz34Params &p, int src_bytes, int dst_bytes, int height, hipStream_t stream);
 /* frame lists for single-kernel plans (video_kernels.hip) */
 void video_frame_list_begin (int n, const void *const *src, void *const *dst, size_t src_size, size_t dst_size);

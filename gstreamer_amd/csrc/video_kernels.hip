@@ -29,6 +29,7 @@
 #include "video_relayout.h"
 #include "video_swizzle34.h"
 #include "video_gamma.h"
+#include "video_dispatch.h"
 
 namespace gstamd {
 
@@ -268,12 +269,6 @@ template <int SEMI, int CH>
 __global__ __launch_bounds__ (256) void k_front_hscale16 (FrontParams f, Planes pl, const int *__restrict__ vpair, ScaleDev sd, uint8_t *__restrict__ dst, int dstride, int ow)
 {
   front_hscale16_lane<SEMI, CH> (f, pl, vpair, sd, dst, dstride, ow, (int) (blockIdx.x * blockDim.x + threadIdx.x), (int) blockIdx.y);
-}
-
-// the 16-bit front inside the first, horizontal u16 pass; false: this front has no specialised form (the caller runs k_front16 + k_scale16)
-bool front_hscale16_usable (const FrontParams &f)
-{
-  return deep_front4_variant (f) >= 0 && !tuning_on ("GSTAMD_NO_CONVERT16_FAST");
 }
 
 hipError_t launch_front_hscale16 (const FrontParams &f, const Planes &pl, const int *vpair_dev, const ScaleDev &sd, uint8_t *dst, int dstride, int ow, hipStream_t stream)
@@ -1136,25 +1131,6 @@ __global__ __launch_bounds__ (256) void k_swizzle34 (Swz34Params p, FrameDeltas 
 
 // map[j]: which source byte of a pixel lands in destination byte j.  src_pos / dst_pos: byte of component c (A, c1, c2, c3) in the
 // source / destination pixel; a 3-byte pixel has no component 0.
-bool swizzle34_setup (int src_bytes, const int *src_pos, int dst_bytes, const int *dst_pos, const uint8_t *src, int sstride, uint8_t *dst, int dstride,
-    int width, Swz34Params *p)
-{
-  if (((uintptr_t) src % 4) != 0 || (sstride % 4) != 0 || ((uintptr_t) dst % 4) != 0 || (dstride % 4) != 0 || (src_bytes == 4 && dst_bytes == 4))
-    return false;
-  uint8_t map[4] = {0, 0, 0, 0};
-  for (int c = dst_bytes == 4 ? 0 : 1; c < 4; c++)
-    map[dst_pos[c]] = c == 0 && src_bytes == 3 ? 0xff : (uint8_t) src_pos[c];
-  memset ((void *) p, 0, sizeof (*p));
-  if (src_bytes == 3 && dst_bytes == 4)
-    swz34_selectors<3, 4> (map, p);
-  else if (src_bytes == 4 && dst_bytes == 3)
-    swz34_selectors<4, 3> (map, p);
-  else
-    swz34_selectors<3, 3> (map, p);
-  p->src = src, p->sstride = sstride, p->dst = dst, p->dstride = dstride, p->width = width;
-  return true;
-}
-
 hipError_t launch_swizzle34 (const Swz34Params &p, int src_bytes, int dst_bytes, int height, hipStream_t stream)
 {
   int nz;
@@ -1413,14 +1389,6 @@ __global__ __launch_bounds__ (256) void k_swizzle4 (const uint8_t *__restrict__ 
 // ------------------------------------------------------------------------------------------------
 // host launchers
 // ------------------------------------------------------------------------------------------------
-static inline bool aligned (const void *p, size_t a) { return ((uintptr_t) p & (a - 1)) == 0; }
-
-bool swizzle4_usable (const FrontParams &f, const Planes &pl, const ColorParams &color, const uint8_t *dst, int dstride)
-{
-  return f.kind == UNPACK_PACKED4 && f.hi_depth == 0 && color.matrix.kind == MATRIX_NONE && color.alpha_kind == ALPHA_NONE && aligned (dst, 16) &&
-      (dstride % 16) == 0 && aligned (pl.p[0], 16) && (pl.stride[0] % 16) == 0;
-}
-
 hipError_t launch_swizzle4 (const FrontParams &f, const Planes &pl, const int pack_pos[4], uint8_t *dst, int dstride, hipStream_t stream)
 {
   const int lanes = (f.width + 3) / 4;
@@ -1890,19 +1858,10 @@ static hipError_t launch_h420_reg_nw (H420RegParams p, int chroma_h, int n_taps,
   return hipGetLastError ();
 }
 
-// regular 4:2:0 horizontal pass into the AYUV intermediate; hipErrorNotSupported: the caller takes the general kernels
+// regular 4:2:0 horizontal pass into the AYUV intermediate, for frames hscale420_reg_frame_ok takes
 hipError_t launch_hscale420_reg (const H420RegParams &p, int chroma_h, int nw, int n_taps, hipStream_t stream)
 {
   video_frame_list_touch (p.dst);
-  if (tuning_on ("GSTAMD_NO_H420_REG"))
-    return hipErrorNotSupported;
-  int ok = (p.width % 16) == 0 && aligned (p.y, 16) && (p.ystride % 16) == 0 && aligned (p.dst, 4) && (p.dstride % 4) == 0;
-  if (p.semi)
-    ok = ok && aligned (p.c0, 16) && (p.cstride % 16) == 0;
-  else
-    ok = ok && aligned (p.c0, 8) && aligned (p.c1, 8) && (p.cstride % 8) == 0;
-  if (!ok)
-    return hipErrorNotSupported;
   switch (nw) {
     case 3: return p.semi ? launch_h420_reg_nw<3, 1> (p, chroma_h, n_taps, stream) : launch_h420_reg_nw<3, 0> (p, chroma_h, n_taps, stream);
     case 4: return p.semi ? launch_h420_reg_nw<4, 1> (p, chroma_h, n_taps, stream) : launch_h420_reg_nw<4, 0> (p, chroma_h, n_taps, stream);
@@ -2081,16 +2040,6 @@ static int bilr_wave_slots ()
   return slots;
 }
 
-static int bil_vec_ok (const BilParams &bp, const Planes &pl)
-{
-  int vec = aligned (pl.p[0], 16) && aligned (pl.p[1], 16) && (pl.stride[0] % 16) == 0 && (pl.stride[1] % 16) == 0;
-  if (bp.planar)
-    /* planar sources only through the straight-line fetch: whole 16-pixel pieces, 8-byte chroma loads */
-    vec = aligned (pl.p[0], 16) && (pl.stride[0] % 16) == 0 && aligned (pl.p[1], 8) && aligned (pl.p[2], 8) && (pl.stride[1] % 8) == 0 &&
-        (pl.stride[2] % 8) == 0 && (bp.fp.width % 16) == 0;
-  return vec;
-}
-
 static hipError_t launch_bilinear420_rows (const BilParams &bp, int chroma_h, int n, const Planes *pl, uint8_t *const *dst, int dstride, hipStream_t stream)
 {
   const int rtiles = (bp.out_w + bp.rows_tile_w - 1) / bp.rows_tile_w;
@@ -2154,15 +2103,6 @@ static hipError_t launch_bilinear420_rows (const BilParams &bp, int chroma_h, in
   return hipGetLastError ();
 }
 
-// the rows kernel takes frames [0, n): every one vectorisable, the destinations 4-byte aligned (the caller checked frame 0's)
-static bool bilinear420_rows_usable (const BilParams &bp, int n, const Planes *pl, uint8_t *const *dst)
-{
-  bool ok = bp.rows != 0 && (bp.fp.width % 16) == 0 && bp.regular_pairs;
-  for (int f = 0; f < n && ok; f++)
-    ok = bil_vec_ok (bp, pl[f]) && aligned (dst[f], 4);
-  return ok;
-}
-
 hipError_t launch_bilinear420 (const BilParams &bp, int chroma_h, const Planes &pl, uint8_t *dst, int dstride, hipStream_t stream)
 {
   int n;
@@ -2176,11 +2116,12 @@ hipError_t launch_bilinear420 (const BilParams &bp, int chroma_h, const Planes &
         pls[f].p[k] += fl.s[f];
     dsts[f] = dst + fl.d[f];
   }
-  bool half = bilinear420_half_usable (bp, n, pls, dsts, dstride), rows = !half && bilinear420_rows_usable (bp, n, pls, dsts);
+  const bool small_ok = tuning_on ("GSTAMD_BIL_HALF_SMALL");
+  bool half = bilinear420_half_usable (bp, n, pls, dsts, dstride, small_ok), rows = !half && bilinear420_rows_usable (bp, n, pls, dsts);
   if (n > 1 && !half && !rows) {
     /* a list the list-taking kernels do not take as a whole: frame 0 alone, the caller goes on frame by frame */
     n = 1;
-    half = bilinear420_half_usable (bp, 1, pls, dsts, dstride), rows = !half && bilinear420_rows_usable (bp, 1, pls, dsts);
+    half = bilinear420_half_usable (bp, 1, pls, dsts, dstride, small_ok), rows = !half && bilinear420_rows_usable (bp, 1, pls, dsts);
   }
   if (n > 1)
     (void) frame_list_for (pl.p[0], dst, &n);
@@ -2190,9 +2131,7 @@ hipError_t launch_bilinear420 (const BilParams &bp, int chroma_h, const Planes &
     return launch_bilinear420_half (bp, chroma_h, n, pls, dsts, dstride, stream);
   if (rows)
     return launch_bilinear420_rows (bp, chroma_h, n, pls, dsts, dstride, stream);
-  const int vec = bil_vec_ok (bp, pl);
-  if (bp.planar && !vec)
-    return hipErrorNotSupported;
+  const int vec = bil_vec_ok (bp, pl);         /* (planar sources: bilinear420_usable saw to it) */
   const int tiles_x = (bp.out_w + bp.tile_w - 1) / bp.tile_w;
   dim3 grid (wide_grid_blocks (tiles_x, bp.out_h));
   const size_t lds_bytes = bil_lds_words (bp.ylen) * 4;

@@ -33,6 +33,7 @@
 #include "../../gstreamer_amd/csrc/video_relayout.h"
 #include "../../gstreamer_amd/csrc/video_swizzle34.h"
 #include "../../gstreamer_amd/csrc/video_v210_fast.h"
+#include "../../gstreamer_amd/csrc/video_dispatch.h"
 
 using namespace gstamd;
 
@@ -50,20 +51,6 @@ static void run_hscale_lds (const SRC &src, const ScaleDev &sd, const Dst &d, in
       for (int x = t0; x < t1; x++)
         hscale_from_lds (lds.data (), lo, sd, d, x, y);
     }
-}
-
-static FastParams emu_fast_params (const VideoPlan &p, bool rgb24 = false)      /* make_fast_params of capi_video.cpp */
-{
-  FastParams fp;
-  fp.width = p.front.width;
-  fp.height = p.front.height;
-  fast_params_finish (fp, p.matrix.p, p.post.pack_pos, p.front.u_plane);
-  /* with a source crop the chroma upsampler still sees the frame's rows above / below the crop (do_unpack_lines :2966) */
-  fp.crow_lo = -(p.rect.in_y >> 1);
-  fp.crow_hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
-  if (rgb24)
-    fast_params_rgb24 (fp, p.matrix.p, p.fout->pos, p.front.u_plane);
-  return fp;
 }
 
 static int emu_packed_ok (const SrcFront &s)           /* front_packed_ok of video_kernels.hip */
@@ -176,8 +163,7 @@ static void run_hscale420 (const SrcFront &src, const ScaleDev &sd, const Dst &d
     }
 }
 
-// k_hscale420_reg: the decision of capi_video.cpp (closed-form pairing) + launch_hscale420_reg (alignment, window words), then the
-// kernel's loop with per-lane register state
+// k_hscale420_reg: the kernel's loop with per-lane register state
 static int g_h420_reg_runs = 0;
 template <int NW, int CH, int SEMI>
 static void run_h420_reg (H420RegParams p, int n_taps)
@@ -343,39 +329,21 @@ static void run_scale_col_src (const ColParams &p, int chroma_h, int semi, const
     run_scale_col_post<OPL, NW, NGV, WSTEP, A8, 0> (p, chroma_h, semi, src, dst, pf, nwaves);
 }
 
-// the decision of capi_video.cpp (build_tables + convert_to_packed) for k_scale_col
+// k_scale_col where the plan, the frame and the destination rows take it; waves and rows per wave are stand-ins for what the library asks the device
 static bool emu_scale_col (const VideoPlan &p, const SrcFront &sf, const Dst &dst, const PostFast &pf)
 {
   int lo, hi;
-  if (getenv ("GSTAMD_NO_COL") || !col_plan_regular (p, &lo, &hi) || sf.pre.matrix.kind != MATRIX_NONE || sf.pre.alpha_kind != ALPHA_NONE)
-    return false;
-  const Planes &pl = sf.pl;
-  const bool semi = p.front.kind == UNPACK_SEMI;
-  if (!semi && pl.stride[p.front.u_plane] != pl.stride[p.front.v_plane])
-    return false;
   ColTables t;
   ColForm f;
   const char *eo = getenv ("GSTAMD_COL_OPL"), *es = getenv ("GSTAMD_COL_SHARE");
-  if (!col_choose (p.passes[0], p.passes[1], p.front.width, p.front.height, eo ? atoi (eo) : 0, !(es && atoi (es) == 0), &t, &f, !getenv ("GSTAMD_COL_NO_REGWIN")))
-    return false;
-  if (((uintptr_t) dst.p % (4 * f.opl)) != 0 || (dst.stride % (4 * f.opl)) != 0)
+  const Planes &pl = sf.pl;
+  const bool semi = p.front.kind == UNPACK_SEMI;
+  if (getenv ("GSTAMD_NO_COL") || !col_plan_ok (p, eo ? atoi (eo) : 0, !(es && atoi (es) == 0), !getenv ("GSTAMD_COL_NO_REGWIN"), &t, &f, &lo, &hi) ||
+      !regular420_frame_ok (p, pl, sf.pre) || !col_dst_ok (f, dst.p, dst.stride))
     return false;
   const char *ew = getenv ("GSTAMD_COL_WAVES"), *er = getenv ("GSTAMD_COL_ROWS");
   const int nwaves = ew && atoi (ew) > 0 ? std::min (atoi (ew), GSTAMD_COL_MAX_WAVES) : 3;
-  ColParams q;
-  memset ((void *) &q, 0, sizeof (q));
-  q.ystride = pl.stride[0];
-  q.cstride = semi ? pl.stride[1] : pl.stride[p.front.u_plane];
-  q.width = p.front.width;
-  q.height = p.front.height;
-  q.u_first = p.front.u_plane != 0;
-  q.crow_lo = lo;
-  q.crow_hi = hi;
-  q.tiles = t.tiles.data ();
-  q.hout = t.hout.data ();
-  q.vrow = t.vrow.data ();
-  q.out_w = p.passes[0].out_size;
-  q.out_h = p.passes[1].out_size;
+  ColParams q = make_col_params (p, pl, lo, hi, t.tiles.data (), t.hout.data (), t.vrow.data (), dst.stride);
   q.n_tiles = (int) t.tiles.size () / 4;
   q.rows_per_wave = std::max (t.min_rows_per_wave, er && atoi (er) > 0 ? atoi (er) : 5);
   q.nwaves = nwaves;
@@ -383,7 +351,6 @@ static bool emu_scale_col (const VideoPlan &p, const SrcFront &sf, const Dst &ds
   q.rows_per_wg = q.rows_per_wave * (nwaves - 1) + q.rows_last;
   q.n_chunks = (q.out_h + q.rows_per_wg - 1) / q.rows_per_wg;
   q.pubn = t.pubn;
-  q.dstride = dst.stride;
   const long long crow_bytes = (long long) q.cstride * (hi - lo) + (semi ? q.width : q.width / 2);
   ColSrc src;
   src.y = col_plane (pl.p[0], 0, (uint32_t) (q.ystride * (q.height - 1) + q.width));
@@ -402,53 +369,20 @@ static bool emu_scale420_fused (const VideoPlan &p, H420RegParams hp, int nw, in
 // returns 1: the horizontal pass went to tmp, 2: the fused kernel rendered the final image, 0: not applicable
 static int emu_hscale420_reg (const VideoPlan &p, const SrcFront &sf, const ScaleDev &sd0, uint8_t *tmp, int tmp_w, const Dst *final_dst, const PostFast *pf)
 {
-  if (getenv ("GSTAMD_NO_H420_REG"))
-    return false;
   const TileGeom g = p.passes[0].horizontal ? pass_tile_geom (p.passes[0]) : TileGeom {0, 0, 0};
-  if (!(p.passes.size () == 2 && p.passes[0].horizontal && p.passes[0].kind == SCALE_NTAP && p.passes[0].dot4_ok && g.tile16_w > 0 &&
-      p.front.chroma_v2 == 1 && kind_has_planes (p.front.kind) && p.front.w_sub == 1 && p.front.h_sub == 1 && !p.matrix_before_scale &&
-      (int) p.vpair.size () >= 2 * p.front.height))
-    return false;
-  const int lo = -(p.rect.in_y >> 1), hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
-  for (int y = 0; y < p.front.height; y++) {
-    int heavy, light;
-    h420r_rows (lo, hi, y, &heavy, &light);
-    const int e0 = p.vpair[2 * y], ta = vpair_row (e0), tb = p.vpair[2 * y + 1];
-    const int th = vpair_role (e0) == 0 ? ta : tb, tl = vpair_role (e0) == 0 ? tb : ta;
-    if (th != heavy || tl != light)
-      return false;
-  }
-  const Planes &pl = sf.pl;
-  const bool semi = p.front.kind == UNPACK_SEMI;
-  if (!semi && pl.stride[p.front.u_plane] != pl.stride[p.front.v_plane])
-    return false;
-  H420RegParams hp;
-  memset (&hp, 0, sizeof (hp));
-  hp.y = pl.p[0];
-  hp.ystride = pl.stride[0];
-  hp.semi = semi;
-  hp.u_first = p.front.u_plane != 0;
-  hp.c0 = semi ? pl.p[1] : pl.p[p.front.u_plane];
-  hp.c1 = semi ? pl.p[1] : pl.p[p.front.v_plane];
-  hp.cstride = semi ? pl.stride[1] : pl.stride[p.front.u_plane];
-  hp.width = p.front.width;
-  hp.height = p.front.height;
-  hp.crow_lo = lo;
-  hp.crow_hi = hi;
-  hp.offset = sd0.offset;
-  hp.tapw = sd0.tapw;
-  hp.nw4 = sd0.nw4;
-  hp.dst = tmp;
-  hp.dstride = tmp_w * 4;
-  hp.out_w = tmp_w;
-  hp.tile_w = g.tile16_w;
-  auto al = [](const void *q, int a) { return ((uintptr_t) q % a) == 0; };
-  bool ok = (hp.width % 16) == 0 && al (hp.y, 16) && (hp.ystride % 16) == 0;
-  ok = ok && (semi ? (al (hp.c0, 16) && (hp.cstride % 16) == 0) : (al (hp.c0, 8) && al (hp.c1, 8) && (hp.cstride % 8) == 0));
-  if (!ok || sd0.nw < 3 || sd0.nw > 5)
-    return false;
-  if (final_dst && emu_scale420_fused (p, hp, sd0.nw, sd0.n_taps, *final_dst, *pf))
+  int lo, hi;
+  if (!hscale420_reg_plan_ok (p, g, &lo, &hi) || !regular420_frame_ok (p, sf.pl, sf.pre))
+    return 0;
+  /* GSTAMD_NO_H420_REG here switches off the fused kernel too (the library's knob of that name leaves it on: there GSTAMD_NO_FUSED420 goes with it) -
+     the tests that want k_hscale420_dot4 set this one name */
+  if (getenv ("GSTAMD_NO_H420_REG"))
+    return 0;
+  const H420RegParams hp0 = make_h420_reg_params (p, sf.pl, lo, hi, sd0, g.tile16_w, tmp, tmp_w * 4);
+  if (final_dst && hscale420_reg_frame_ok (hp0, sd0.nw, final_dst->p, final_dst->stride) && emu_scale420_fused (p, hp0, sd0.nw, sd0.n_taps, *final_dst, *pf))
     return 2;
+  if (!hscale420_reg_frame_ok (hp0, sd0.nw, hp0.dst, hp0.dstride))
+    return 0;
+  H420RegParams hp = hp0;
   const char *e = getenv ("GSTAMD_H420_ROWS");
   int lpw = e && atoi (e) > 0 ? atoi (e) : 12;
   hp.lines_per_wave = std::max (4, (lpw + 1) & ~1);
@@ -614,13 +548,12 @@ static void run_fused420_ch (const Fused420Params &p, int chroma_h, const Dst &d
     run_fused420<NW, CHROMA_H_NONE, SEMI> (p, dst, pf, nwaves);
 }
 
-// the decision of capi_video.cpp (ensure_tables + convert_to_packed) for k_scale420_fused; hp = the k_hscale420_reg parameters
+// k_scale420_fused behind the k_hscale420_reg gates; hp = the k_hscale420_reg parameters.  Waves, rows per chunk and ring are stand-ins for
+// what the library asks the device (fused_pick_geometry)
 static bool emu_scale420_fused (const VideoPlan &p, H420RegParams hp, int nw, int n_taps_h, const Dst &dst, const PostFast &pf)
 {
-  if (getenv ("GSTAMD_NO_FUSED420") || p.passes[1].horizontal || p.passes[1].kind != SCALE_NTAP || nw < 3 || nw > 5)
-    return false;
   Fused420Tables t;
-  if (!make_fused420_tables (p.passes[1], p.front.height, &t))
+  if (getenv ("GSTAMD_NO_FUSED420") || !fused420_plan_ok (p, &t))
     return false;
   const char *ew = getenv ("GSTAMD_FUSED_WAVES"), *er = getenv ("GSTAMD_FUSED_ROWS");
   const int nwaves = ew && atoi (ew) > 0 ? atoi (ew) : 8;
@@ -640,8 +573,6 @@ static bool emu_scale420_fused (const VideoPlan &p, H420RegParams hp, int nw, in
   if (getenv ("GSTAMD_FUSED_RING_SHORT"))        /* tests: a ring one slot too short must break the picture (the emulator's wave order shows it) */
     q.ring -= 1;
   q.n_groups = t.n_groups;
-  if (((uintptr_t) dst.p % 4) != 0 || (dst.stride % 4) != 0)
-    return false;
   g_fused_runs++;
   if (nw == 3)
     hp.semi ? run_fused420_ch<3, 1> (q, p.front.chroma_h, dst, pf, nwaves) : run_fused420_ch<3, 0> (q, p.front.chroma_h, dst, pf, nwaves);
@@ -793,23 +724,12 @@ extern "C" int emu_gamma_fused_runs (void) { return g_gamma_fused_runs; }
 extern "C" int emu_h420_runs (void) { return g_h420_runs; }
 extern "C" int emu_h420_reg_runs (void) { return g_h420_reg_runs; }
 
-// k_swizzle34 (video_kernels.hip swizzle34_setup + the kernel's grid)
+// k_swizzle34 over its grid
 static bool emu_swizzle34 (int sb, const int *src_pos, int db, const int *dst_pos, const uint8_t *src, int sstride, uint8_t *dst, int dstride, int width, int height)
 {
-  if (((uintptr_t) src % 4) != 0 || (sstride % 4) != 0 || ((uintptr_t) dst % 4) != 0 || (dstride % 4) != 0 || getenv ("EMU_NO_SWIZZLE34"))
-    return false;
-  uint8_t map[4] = {0, 0, 0, 0};
-  for (int c = db == 4 ? 0 : 1; c < 4; c++)
-    map[dst_pos[c]] = c == 0 && sb == 3 ? 0xff : (uint8_t) src_pos[c];
   Swz34Params sp;
-  memset ((void *) &sp, 0, sizeof (sp));
-  if (sb == 3 && db == 4)
-    swz34_selectors<3, 4> (map, &sp);
-  else if (sb == 4 && db == 3)
-    swz34_selectors<4, 3> (map, &sp);
-  else
-    swz34_selectors<3, 3> (map, &sp);
-  sp.src = src, sp.sstride = sstride, sp.dst = dst, sp.dstride = dstride, sp.width = width;
+  if (getenv ("EMU_NO_SWIZZLE34") || !swizzle34_setup (sb, src_pos, db, dst_pos, src, sstride, dst, dstride, width, &sp))
+    return false;
   for (int y = 0; y < height; y++)
     for (int lane = 0; lane < ((width + 3) / 4 + 255) / 256 * 256; lane++) {
       if (sb == 3 && db == 4)
@@ -1638,6 +1558,13 @@ extern "C" int emu_video_convert (const GstAmdVideoInfo *in, const GstAmdVideoIn
   return r;
 }
 
+// pass i of the plan with its tables where they are (the library keeps the byte-dot-product words only of passes that take them)
+static ScaleDev pass_scale_dev (const VideoPlan &p, size_t i)
+{
+  const ScalePass &sp = p.passes[i];
+  return make_scale_dev (sp, sp.offset.data (), sp.taps.data (), sp.dot4_ok ? sp.tapw.data () : nullptr);
+}
+
 static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, const Planes &pl, uint8_t *d0, int dstride, int vec_ok, bool rgb24)
 {
   ColorParams color, none;
@@ -1646,10 +1573,10 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
   color.alpha_kind = p.post.alpha_kind;
   color.alpha_value = p.post.alpha_value;
   const int *vpair = p.vpair.data ();
-  if (p.passes.empty () && p.fast_pair && vec_ok) {
+  if (vec_ok && fast_pair_usable (p, pl, d0, dstride, rgb24 ? 4 : 16)) {
     /* vec_ok: 1 = shipped configuration (strip kernel, 3 line pairs per lane); 100 + K = strip kernel with K pairs;
      * 200 + K = wide kernel (LDS-staged 1024-px runs) with K pairs per wave */
-    FastParams fp = emu_fast_params (p, rgb24);
+    FastParams fp = make_fast_params (p, rgb24);
     const int pairs = fp.height / 2 + 1;
     const int lay = GSTAMD_LAYOUT (fp.pack_pos[1], fp.pack_pos[2], fp.pack_pos[3]);
 #define FOR_LAYOUT(CH, CALL) \
@@ -1723,47 +1650,31 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
 #undef FOR_LAYOUT
     return GSTAMD_OK;
   }
-  if (p.fast_420p && vec_ok && ((uintptr_t) pl.p[0] % 8) == 0 && (pl.stride[0] % 8) == 0 && ((uintptr_t) pl.p[1] % 4) == 0 && ((uintptr_t) pl.p[2] % 4) == 0 &&
-      (pl.stride[1] % 4) == 0 && pl.stride[1] == pl.stride[2] && ((uintptr_t) d0 % 16) == 0 && (dstride % 16) == 0 &&
-      getenv ("GSTAMD_NO_FAST420P") == nullptr) {        /* k_convert420p */
-    Fast420pParams q;
-    q.fp = emu_fast_params (p);
-    q.y = pl.p[0];
-    q.u = pl.p[p.front.u_plane];
-    q.v = pl.p[p.front.v_plane];
-    q.ystride = pl.stride[0];
-    q.cstride = pl.stride[1];
+  if (vec_ok && convert420p_usable (p, pl, d0, dstride) && getenv ("GSTAMD_NO_FAST420P") == nullptr) {        /* k_convert420p */
+    const Fast420pParams q = make_fast420p_params (p, pl);
     g_fast420p_runs++;
     for (int r = 0; r < (p.front.height + 1) / 2; r++)
       for (int x0 = 0; x0 < p.front.width; x0 += 8)
         convert420p_lane8x2 (q, d0, dstride, x0, r);
     return GSTAMD_OK;
   }
-  if (p.fast_422 && vec_ok && ((uintptr_t) pl.p[0] % 16) == 0 && (pl.stride[0] % 16) == 0 && ((uintptr_t) d0 % 16) == 0 && (dstride % 16) == 0 &&
-      getenv ("GSTAMD_NO_FAST422") == nullptr) {        /* k_convert422 */
-    Fast422Params q;
-    q.fp = emu_fast_params (p);
-    q.chroma_h = p.front.chroma_h;
-    fast422_selectors (p.front.pos[1], p.front.pos[2], p.front.pos[3], &q);
+  if (vec_ok && convert422_usable (p, false, pl, d0, dstride) && getenv ("GSTAMD_NO_FAST422") == nullptr) {        /* k_convert422 */
+    const Fast422Params q = make_fast422_params (p, false);
     g_fast422_runs++;
     for (int y = 0; y < p.front.height; y++)
       for (int x0 = 0; x0 < p.front.width; x0 += 8)
         convert422_lane8_any (q, pl.p[0] + (size_t) y * pl.stride[0], d0 + (size_t) y * dstride, x0);
     return GSTAMD_OK;
   }
-  if (p.fast_422_ayuv && !g_gamma_hook && !rgb24 && ((uintptr_t) pl.p[0] % 16) == 0 && (pl.stride[0] % 16) == 0 && ((uintptr_t) d0 % 16) == 0 && (dstride % 16) == 0 &&
-      getenv ("GSTAMD_NO_FAST422") == nullptr) {        /* k_convert422_ayuv */
-    Fast422Params q;
-    memset ((void *) &q, 0, sizeof (q));
-    q.fp.width = p.front.width;
-    q.fp.height = p.front.height;
-    q.chroma_h = p.front.chroma_h;
-    fast422_selectors (p.front.pos[1], p.front.pos[2], p.front.pos[3], &q);
+  if (!g_gamma_hook && !rgb24 && convert422_usable (p, true, pl, d0, dstride) && getenv ("GSTAMD_NO_FAST422") == nullptr) {        /* k_convert422_ayuv */
+    const Fast422Params q = make_fast422_params (p, true);
     for (int y = 0; y < p.front.height; y++)
       for (int x0 = 0; x0 < p.front.width; x0 += 8)
         convert422_lane8_ayuv (q, pl.p[0] + (size_t) y * pl.stride[0], d0 + (size_t) y * dstride, x0);
     return GSTAMD_OK;
   }
+  if (p.deep16 && deep16_refusal (p, pl, d0, dstride))
+    return GSTAMD_ERR_UNSUPPORTED;
   if (p.deep16 && p.passes.empty ()) {     /* k_convert16 */
     for (int y = 0; y < p.front.height; y++)
       for (int x0 = 0; x0 < p.front.width; x0 += 4)
@@ -1771,8 +1682,8 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
     return GSTAMD_OK;
   }
   DeepPackParams ds4;
-  if (p.deep16 && !p.matrix_before_scale && !g_gamma_hook && getenv ("GSTAMD_NO_DEEP_SCALE_PACK") == nullptr && deep_scale4_plan_ok (p, &ds4) && ((uintptr_t) d0 % 4) == 0 &&
-      (dstride % 4) == 0) {         /* k_deep_scale4 over its grid */
+  if (p.deep16 && !p.matrix_before_scale && !g_gamma_hook && getenv ("GSTAMD_NO_DEEP_SCALE_PACK") == nullptr && deep_scale4_plan_ok (p, &ds4) &&
+      rows_aligned (d0, dstride, 4)) {         /* k_deep_scale4 over its grid */
     ds4.pl = pl;
     ds4.vpair = vpair;
     ds4.sh.offset = p.passes[0].offset.data (), ds4.sh.taps = p.passes[0].taps.data ();
@@ -1783,7 +1694,7 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
         deep_scale4_any (deep_pack_variant (p.front), ds4, p.deep, p.post, d0, dstride, 4 * l, y);
     return GSTAMD_OK;
   }
-  if (p.deep16 && !p.matrix_before_scale) {        /* convert_deep_scaled: k_front16, k_scale16 ..., k_scale16_final */
+  if (p.deep16 && !p.matrix_before_scale) {        /* k_front16, k_scale16 ..., k_scale16_final */
     const int in_w = p.front.width, in_h = p.front.height;
     std::vector<uint8_t> a ((size_t) in_w * in_h * 8), b;
     for (int y = 0; y < in_h; y++)
@@ -1791,14 +1702,9 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
         front16_lane4 (p.front, pl, vpair, a.data (), in_w * 8, x0, y);
     Deep16Image cur = {a.data (), in_w * 8, in_w, in_h};
     size_t first = 0;
-    if (p.passes.size () == 2 && p.passes[0].horizontal && deep_front4_variant (p.front) >= 0 && !getenv ("EMU_NO_CONVERT16_FAST")) {
+    if (p.passes.size () == 2 && p.passes[0].horizontal && front_hscale16_usable (p.front, !getenv ("EMU_NO_CONVERT16_FAST"))) {
       /* k_front_hscale16: the front inside the first, horizontal pass */
-      ScaleDev sd16;
-      memset (&sd16, 0, sizeof (sd16));
-      sd16.kind = p.passes[0].kind;
-      sd16.n_taps = p.passes[0].n_taps;
-      sd16.offset = p.passes[0].offset.data ();
-      sd16.taps = p.passes[0].taps.data ();
+      const ScaleDev sd16 = pass_scale_dev (p, 0);
       const int ow = p.passes[0].out_size;
       b.assign ((size_t) ow * in_h * 8, 0);
       for (int y = 0; y < in_h; y++)
@@ -1811,12 +1717,7 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
     for (size_t i = first; i < p.passes.size (); i++) {
       const bool hz = p.passes[i].horizontal, last = i + 1 == p.passes.size ();
       const int ow = hz ? p.passes[i].out_size : cur.width, oh = hz ? cur.height : p.passes[i].out_size;
-      ScaleDev sd16;
-      memset (&sd16, 0, sizeof (sd16));
-      sd16.kind = p.passes[i].kind;
-      sd16.n_taps = p.passes[i].n_taps;
-      sd16.offset = p.passes[i].offset.data ();
-      sd16.taps = p.passes[i].taps.data ();
+      const ScaleDev sd16 = pass_scale_dev (p, i);
       if (!last)
         b.assign ((size_t) ow * oh * 8, 0);
       for (int y = 0; y < oh; y++)
@@ -1831,8 +1732,7 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
     return GSTAMD_OK;
   }
   /* launch_convert's 16-byte path for 4-byte packed sources */
-  if (p.passes.empty () && vec_ok && p.front.kind == UNPACK_PACKED4 && ((uintptr_t) d0 % 16) == 0 && (dstride % 16) == 0 && ((uintptr_t) pl.p[0] % 16) == 0 &&
-      (pl.stride[0] % 16) == 0)
+  if (p.passes.empty () && vec_ok && p.front.kind == UNPACK_PACKED4 && rows_aligned (d0, dstride, 16) && plane_aligned (pl, 0, 16))
     vec_ok = 2;
   else if (p.passes.empty () && p.front.kind == UNPACK_PACKED4 && vec_ok == 2)
     vec_ok = 1;
@@ -1858,10 +1758,10 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
       }
     return GSTAMD_OK;
   }
-  if (p.passes.empty () && p.front.kind == UNPACK_PACKED3 && p.front.hi_depth == 0 && color.matrix.kind == MATRIX_NONE && color.alpha_kind == ALPHA_NONE &&
+  if (p.passes.empty () && p.front.kind == UNPACK_PACKED3 && p.front.hi_depth == 0 && color_is_none (color) &&
       !rgb24 && emu_swizzle34 (3, p.front.pos, 4, p.post.pack_pos, pl.p[0], pl.stride[0], d0, dstride, p.front.width, p.front.height))
     return GSTAMD_OK;
-  if (p.passes.empty () && vec_ok == 2 && p.front.hi_depth == 0 && color.matrix.kind == MATRIX_NONE && color.alpha_kind == ALPHA_NONE) {
+  if (p.passes.empty () && vec_ok && swizzle4_usable (p.front, pl, color, d0, dstride)) {
     /* k_swizzle4: a byte permutation per pixel, four pixels per lane */
     const uint32_t sel = swizzle4_selector (p.front.pos, p.post.pack_pos);
     g_swizzle4_runs++;
@@ -1895,16 +1795,8 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
   const ColorParams &pre = p.matrix_before_scale ? color : none;
   const ColorParams &post = p.matrix_before_scale ? none : color;
   ScaleDev sd[2];
-  for (size_t i = 0; i < p.passes.size (); i++) {
-    sd[i].kind = p.passes[i].kind;
-    sd[i].n_taps = p.passes[i].n_taps;
-    sd[i].inc = p.passes[i].inc;
-    sd[i].offset = p.passes[i].offset.data ();
-    sd[i].taps = p.passes[i].taps.data ();
-    sd[i].tapw = p.passes[i].dot4_ok ? p.passes[i].tapw.data () : nullptr;
-    sd[i].nw = p.passes[i].nw;
-    sd[i].nw4 = p.passes[i].nw4;
-  }
+  for (size_t i = 0; i < p.passes.size (); i++)
+    sd[i] = pass_scale_dev (p, i);
   SrcFront sf;
   sf.f = p.front;
   sf.pl = pl;
@@ -1923,9 +1815,9 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
   PostFast pf, pf_none;
   memset (&pf_none, 0, sizeof (pf_none));
   pf.use = p.fast_post ? 1 : 0;
-  pf.fp = emu_fast_params (p);
+  pf.fp = make_fast_params (p);
   if (p.deep16) {
-    /* convert_deep_scaled, the picture grows: the convert stage first (k_convert16 into an 8-bit unpack-order image), then the
+    /* the picture grows: the convert stage first (k_convert16 into an 8-bit unpack-order image), then the
      * 8-bit scalers from that image */
     const int in_w = p.front.width, in_h = p.front.height;
     std::vector<uint8_t> a ((size_t) in_w * in_h * 4), b;
@@ -1953,92 +1845,33 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
     }
     return GSTAMD_OK;
   }
-  const auto small_kind = [](int k) { return k == SCALE_NEAREST || k == SCALE_2TAP; };
-  if (p.passes.size () == 2 && small_kind (p.passes[0].kind) && small_kind (p.passes[1].kind)) {
+  if (bilinear_plan (p)) {
     const bool h_first = p.passes[0].horizontal;
     const ScaleDev &sh = h_first ? sd[0] : sd[1], &sv = h_first ? sd[1] : sd[0];
     const Dst d = mk (d0, dstride, true);
     const int span = p.passes[h_first ? 0 : 1].max_span;
     const TileGeom g = pass_tile_geom (p.passes[h_first ? 0 : 1]);
-    int bil_yl = 0;
-    const int bil_tw = vec_ok >= 400 ? vec_ok - 400 : bil_pick_tile (p.out_info.width, p.passes[0].inc, &bil_yl);     /* 400 + w: tiles of w outputs */
-    if (vec_ok >= 400)
-      bil_yl = bil_ylen (p.out_info.width, p.passes[0].inc, bil_tw);
-    const bool bil_ayuv = bilinear420_ayuv_plan (p) && getenv ("GSTAMD_NO_BILINEAR_AYUV") == nullptr;          /* bilinear420_params of capi_video.cpp */
-    const bool bil_planar = p.front.kind == UNPACK_PLANAR;
-    const bool bil_planar_ok = bil_planar && ((uintptr_t) pl.p[0] % 16) == 0 && pl.stride[0] % 16 == 0 && ((uintptr_t) pl.p[1] % 8) == 0 &&
-        ((uintptr_t) pl.p[2] % 8) == 0 && pl.stride[1] % 8 == 0 && pl.stride[2] % 8 == 0 && (p.front.width % 16) == 0;
-    if (h_first && p.passes[0].kind == SCALE_2TAP && p.passes[1].kind == SCALE_2TAP && (p.front.kind == UNPACK_SEMI || bil_planar_ok) && p.front.w_sub == 1 &&
-        p.front.h_sub == 1 && !p.matrix_before_scale && (p.fast_post || bil_ayuv) && (!p.out_planar || bil_ayuv) && p.front.chroma_v2 != 2 && bil_tw > 0 && bil_yl > 0 && vec_ok != 300) {
-      /* k_bilinear420 (video_bilinear_fast.h); vec_ok == 300 selects the generic tile kernel below instead */
-      BilParams bp;
-      bp.fp = pf.fp;
-      bp.fp.ayuv = bil_ayuv ? (p.matrix.kind == MATRIX_NONE ? 1 : 2) : 0;
-      bp.fp.m8 = p.matrix;
-      if (bil_ayuv)
+    /* vec_ok 400 + w: k_bilinear420 with tiles of w outputs; 300: the generic tile kernel below instead of the 4:2:0 bilinear kernels */
+    const BilKnobs bk = {vec_ok != 300, getenv ("GSTAMD_NO_BILINEAR_AYUV") == nullptr, false, getenv ("EMU_NO_BILINEAR_ROWS") == nullptr,
+      getenv ("EMU_NO_BILINEAR_HALF") == nullptr, vec_ok >= 400 ? vec_ok - 400 : -1, getenv ("EMU_BIL_ROWS_TILE") ? atoi (getenv ("EMU_BIL_ROWS_TILE")) : -1};
+    BilParams bp;
+    if (rows_aligned (d0, dstride, 4) && bilinear420_params (p, bk, sd[1].offset, sd[1].taps, vpair, &bp) && bilinear420_usable (bp, pl, d0, dstride)) {
+      if (bp.fp.ayuv)
         g_bil_ayuv_runs++;
-      bp.out_w = p.out_info.width;
-      bp.out_h = p.out_info.height;
-      bp.inc = p.passes[0].inc;
-      bp.tile_w = bil_tw;
-      bp.ylen = bil_yl;
-      bp.voffset = sd[1].offset;
-      bp.vtaps = sd[1].taps;
-      bp.vpair = p.front.chroma_v2 ? vpair : nullptr;
-      const bool vec = bil_planar ? true : (((uintptr_t) pl.p[0] | (uintptr_t) pl.p[1]) % 16) == 0 && pl.stride[0] % 16 == 0 && pl.stride[1] % 16 == 0;
-      bp.planar = bil_planar ? 1 : 0;
-      bp.u_plane = p.front.u_plane;
-      bp.v_plane = p.front.v_plane;
+      const int vec = bil_vec_ok (bp, pl);
+      const Planes *pls = &pl;
+      uint8_t *const dsts[1] = {d0};
       g_bil_runs++;
       const int lay = bp.fp.ayuv ? GSTAMD_LAYOUT_AYUV : GSTAMD_LAYOUT (bp.fp.pack_pos[1], bp.fp.pack_pos[2], bp.fp.pack_pos[3]);
       std::vector<uint32_t> lds_w (bil_lds_words (bp.ylen));
       const BilLds lds = bil_lds (lds_w.data (), bp.ylen);
 #define BIL_L(CH, pr, pg, pb) if (lay == GSTAMD_LAYOUT (pr, pg, pb)) bil_emit<CH, GSTAMD_LAYOUT (pr, pg, pb)> (bp, d0, dstride, t0, t1, y, r0, lane, &lds);
 #define BIL(CH) { BIL_L (CH, 2, 1, 0) BIL_L (CH, 0, 1, 2) BIL_L (CH, 1, 2, 3) BIL_L (CH, 3, 2, 1) BIL_L (CH, 0, 0, 4) }
-      bp.regular_pairs = 0;
-      bp.rows = 0;
+      /* launch_bilinear420's order: the halving kernel, the rows kernel, k_bilinear420.  small_ok: the device keeps single frames of less than 4 M outputs
+       * off the halving kernel for speed - the goldens are that small, and its body is held to them here */
       {
-        /* k_bilinear420_rows (video_bilinear_rows.h): the gate of capi_video.cpp, here against the pairing table itself */
-        bool fits = p.front.chroma_v2 && vec && (p.front.width % 16) == 0 && getenv ("EMU_NO_BILINEAR_ROWS") == nullptr;
-        if (getenv ("EMU_BILR_DEBUG"))
-          fprintf (stderr, "bilr gate: v2 %d vec %d w %d\n", (int) p.front.chroma_v2, (int) vec, p.front.width);
-        for (int y = 0; y < bp.out_h && fits; y++) {
-          fits = bilr_window_matches (bp, (int) bp.voffset[y]);
-          if (!fits && getenv ("EMU_BILR_DEBUG")) {
-            int ra, rb, role, wa, wb, wc;
-            bilr_window (bp, (int) bp.voffset[y], &wa, &wb, &wc);
-            fprintf (stderr, "bilr gate: y %d r0 %d window %d %d %d\n", y, (int) bp.voffset[y], wa, wb, wc);
-            for (int l = 0; l < 2; l++) {
-              bil_rows (bp, (int) bp.voffset[y] + l, &ra, &rb, &role);
-              fprintf (stderr, "   line %d: ra %d rb %d role %d\n", (int) bp.voffset[y] + l, ra, rb, role);
-            }
-          }
-        }
-        int rows_ylen = 0;
-        bp.rows_tile_w = getenv ("EMU_BIL_ROWS_TILE") ? atoi (getenv ("EMU_BIL_ROWS_TILE")) : bilr_pick_tile (bp.out_w, bp.inc, &rows_ylen);
-        if (getenv ("EMU_BIL_ROWS_TILE"))
-          rows_ylen = bil_ylen (bp.out_w, bp.inc, bp.rows_tile_w);
-        fits = fits && bp.rows_tile_w > 0 && rows_ylen > 0;
-        if (fits)
-          bp.rows = getenv ("EMU_BIL_ROWS") ? atoi (getenv ("EMU_BIL_ROWS")) : 4;
-      }
-      if (bp.rows != 0 && p.front.chroma_v2 && getenv ("EMU_NO_BILINEAR_HALF") == nullptr) {
-        /* k_bilinear420_half (video_bilinear_half.h): capi_video.cpp's gate - the pairing table is the closed form, the halving exact - and
-         * bilinear420_half_usable's alignment rules */
-        BilParams hp = bp;
-        hp.regular_pairs = 1;
-        bool regular = true;
-        for (int y = 0; y < bp.out_h && regular; y++)
-          for (int l = 0; l < 2 && regular; l++) {
-            const int line = (int) bp.voffset[y] + l;
-            int ra, rb, role;
-            bil_rows (hp, line, &ra, &rb, &role);
-            const int e0 = vpair[2 * line], ta = vpair_row (e0), trole = vpair_role (e0), tb = vpair[2 * line + 1];
-            regular = ta == ra && tb == rb && (ra == rb || trole == role);
-          }
-        const bool al = ((uintptr_t) pl.p[0] % 16) == 0 && pl.stride[0] % 16 == 0 && ((uintptr_t) d0 % 16) == 0 && dstride % 16 == 0 &&
-            (bil_planar ? bil_planar_ok : (((uintptr_t) pl.p[1] % 16) == 0 && pl.stride[1] % 16 == 0));
-        if (regular && al && bilh_plan_ok (hp, bp.voffset, bp.vtaps)) {
+        if (bilinear420_half_usable (bp, 1, pls, dsts, dstride, true)) {
+          BilParams hp = bp;
           g_bilh_runs++;
           const int tiles = (hp.fp.width + BILH_TILE_SRC - 1) / BILH_TILE_SRC;
           const int rows = getenv ("EMU_BIL_HALF_ROWS") ? atoi (getenv ("EMU_BIL_HALF_ROWS")) : 5;
@@ -2066,7 +1899,8 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
           return GSTAMD_OK;
         }
       }
-      if (bp.rows != 0) {
+      if (bilinear420_rows_usable (bp, 1, pls, dsts)) {
+        bp.rows = getenv ("EMU_BIL_ROWS") ? atoi (getenv ("EMU_BIL_ROWS")) : 4;          /* stand-in for the strips the launcher sizes by the device's wave slots */
         g_bilr_runs++;
         static BilrState st[64];
         static BilrLane lc[64];
@@ -2136,20 +1970,34 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
 #undef BIL_L
       return GSTAMD_OK;
     }
-    if (p.matrix_before_scale && p.front.kind != UNPACK_PACKED4 && p.front.hi_depth == 0 && ((uintptr_t) d0 % 4) == 0 && (dstride % 4) == 0 &&
-        !getenv ("EMU_NO_BILINEAR4")) {
+    PlanePlan raw4;
+    if (plane_raw4_plan (p, &raw4) && getenv ("GSTAMD_NO_PLANE_QUAD") == nullptr) {          /* k_plane_quad on 4-byte pixels */
+      PlaneJob J;
+      memset ((void *) &J, 0, sizeof (J));
+      J.kind = PLANE_SCALE;
+      J.s = {pl.p[0], pl.stride[0], 4, 0};
+      J.d = {d0, dstride, 4};
+      J.iw = raw4.iw, J.ih = raw4.ih, J.ow = raw4.ow, J.oh = raw4.oh;
+      J.n_pass = 2;
+      J.h_first = h_first ? 1 : 0;
+      J.pass[h_first ? 0 : 1] = sh, J.pass[h_first ? 1 : 0] = sv;
+      J.dstep = getenv ("GSTAMD_PLANE_QUAD_NO_DSTEP") ? 0 : plane_quad_dstep (raw4);
+      J.quad = 1 + QUAD_8;
+      g_emu_quad_runs++;
+      const int rows = getenv ("GSTAMD_PLANE_QUAD_ROWS") ? atoi (getenv ("GSTAMD_PLANE_QUAD_ROWS")) : 3;
+      const int lanes = (((J.ow * 4 + 7) / 8 + 63) / 64) * 64;
+      for (int y0 = 0; y0 < J.oh; y0 += rows)
+        for (int lane = 0; lane < lanes; lane++)
+          plane_rows_body (J, lane, y0, rows);
+      return GSTAMD_OK;
+    }
+    if (bilinear4_pre_usable (p, d0, dstride) && !getenv ("EMU_NO_BILINEAR4")) {
       /* enlarging from planes / packed 4:2:2: k_convert at the source's size into an A, c1, c2, c3 image, then k_bilinear4_rows from it */
       const int in_w = p.front.width, in_h = p.front.height;
       std::vector<uint32_t> img ((size_t) in_w * in_h);
-      if (p.fast_pre && vec_ok && ((uintptr_t) pl.p[0] % 4) == 0 && (pl.stride[0] % 4) == 0 && ((uintptr_t) pl.p[1] % 4) == 0 && (pl.stride[1] % 4) == 0 &&
-          !getenv ("GSTAMD_NO_FAST_PRE")) {
-        /* capi_video.cpp: the line-pair kernel (k_convert_strip, byte order A, R, G, B) makes the source-size image */
-        FastParams fp;
-        fp.width = in_w, fp.height = in_h;
-        const int ident[4] = {0, 1, 2, 3};
-        fast_params_finish (fp, p.matrix.p, ident, p.front.u_plane);
-        fp.crow_lo = -(p.rect.in_y >> 1);
-        fp.crow_hi = ((p.rect.in_maxh + 1) >> 1) - 1 - (p.rect.in_y >> 1);
+      if (vec_ok && fast_pre_usable (p, pl) && !getenv ("GSTAMD_NO_FAST_PRE")) {
+        /* the line-pair kernel (k_convert_strip, byte order A, R, G, B) makes the source-size image */
+        FastParams fp = make_fast_pre_params (p);
         fp.store_policy = 1;
         const int pairs = fp.height / 2 + 1, K = 3;
         uint8_t *im = (uint8_t *) img.data ();
@@ -2178,27 +2026,6 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
       for (int y0 = 0; y0 < b.out_h; y0 += b.rows)
         for (int x0 = 0; x0 < b.out_w; x0 += 4)
           bilinear4_rows_lane (b, d, pf_none, x0, y0);
-      return GSTAMD_OK;
-    }
-    PlanePlan raw4;
-    if (plane_raw4_plan (p, &raw4) && getenv ("GSTAMD_NO_PLANE_QUAD") == nullptr) {          /* k_plane_quad on 4-byte pixels */
-      PlaneJob J;
-      memset ((void *) &J, 0, sizeof (J));
-      J.kind = PLANE_SCALE;
-      J.s = {pl.p[0], pl.stride[0], 4, 0};
-      J.d = {d0, dstride, 4};
-      J.iw = raw4.iw, J.ih = raw4.ih, J.ow = raw4.ow, J.oh = raw4.oh;
-      J.n_pass = 2;
-      J.h_first = h_first ? 1 : 0;
-      J.pass[h_first ? 0 : 1] = sh, J.pass[h_first ? 1 : 0] = sv;
-      J.dstep = getenv ("GSTAMD_PLANE_QUAD_NO_DSTEP") ? 0 : plane_quad_dstep (raw4);
-      J.quad = 1 + QUAD_8;
-      g_emu_quad_runs++;
-      const int rows = getenv ("GSTAMD_PLANE_QUAD_ROWS") ? atoi (getenv ("GSTAMD_PLANE_QUAD_ROWS")) : 3;
-      const int lanes = (((J.ow * 4 + 7) / 8 + 63) / 64) * 64;
-      for (int y0 = 0; y0 < J.oh; y0 += rows)
-        for (int lane = 0; lane < lanes; lane++)
-          plane_rows_body (J, lane, y0, rows);
       return GSTAMD_OK;
     }
     if (p.front.kind == UNPACK_PACKED4 && p.front.hi_depth == 0 && sf.pre.matrix.kind == MATRIX_NONE && sf.pre.alpha_kind == ALPHA_NONE &&
@@ -2272,9 +2099,7 @@ static int emu_convert_packed (const VideoPlan &p, const GstAmdVideoInfo *in, co
         scale2x2_body<SrcFront> (sf, sh, sv, h_first ? 1 : 0, d, p.out_info.width, p.out_info.height, x, y);
     return GSTAMD_OK;
   }
-  /* convert_to_packed's raw4: an identity-unpack 4-byte source without a colour step before the scaler goes to the image kernels */
-  const bool raw4 = p.front.kind == UNPACK_PACKED4 && p.front.pos[0] == 0 && p.front.pos[1] == 1 && p.front.pos[2] == 2 && p.front.pos[3] == 3 &&
-      sf.pre.matrix.kind == MATRIX_NONE && sf.pre.alpha_kind == ALPHA_NONE && ((uintptr_t) pl.p[0] % 4) == 0 && (pl.stride[0] % 4) == 0;
+  const bool raw4 = raw4_source (p, pre, pl);
   SrcImage raw_img;
   raw_img.p = pl.p[0];
   raw_img.stride = pl.stride[0];
