@@ -163,8 +163,15 @@ class AudioResampler:
 
 
 # ---- GstAudioConverter (include/gstamd_audio.h) -------------------------------------------------------------------------------
-AFMT = {"S8": 2, "U8": 3, "S16LE": 4, "S24_32LE": 8, "S32LE": 12, "S24LE": 16, "F32LE": 28, "F64LE": 30}
-AFMT_BYTES = {"S8": 1, "U8": 1, "S16LE": 2, "S24LE": 3, "S24_32LE": 4, "S32LE": 4, "F32LE": 4, "F64LE": 8}
+# all 31 raw GstAudioFormats (audio-format.h:80-130): 4 .. 27 in groups of LE, BE, unsigned LE, unsigned BE
+AFMT = {"S8": 2, "U8": 3, "F32LE": 28, "F32BE": 29, "F64LE": 30, "F64BE": 31}
+AFMT_BYTES = {"S8": 1, "U8": 1, "F32LE": 4, "F32BE": 4, "F64LE": 8, "F64BE": 8}
+AFMT_DEPTH = {"S8": 8, "U8": 8}
+for _g, (_n, _bytes) in enumerate((("16", 2), ("24_32", 4), ("32", 4), ("24", 3), ("20", 3), ("18", 3))):
+    for _k, (_sign, _end) in enumerate((("S", "LE"), ("S", "BE"), ("U", "LE"), ("U", "BE"))):
+        AFMT[_sign + _n + _end] = 4 + 4 * _g + _k
+        AFMT_BYTES[_sign + _n + _end] = _bytes
+        AFMT_DEPTH[_sign + _n + _end] = int(_n.split("_")[0])
 DITHER = {"none": 0, "rpdf": 1, "tpdf": 2, "tpdf-hf": 3}
 NOISE_SHAPING = {"none": 0, "error-feedback": 1, "simple": 2, "medium": 3, "high": 4}
 MAX_CHANNELS = 8

@@ -22,33 +22,48 @@ static int aconv_fail (int code, const std::string &msg)
   return code;
 }
 
-// ---- kernels: one lane per sample -----------------------------------------------------------------------------------------------
-__global__ __launch_bounds__ (256) void k_aconv_pre (AConvPlan p, const uint8_t *__restrict__ in, uint8_t *__restrict__ mid, size_t frames)
+// ---- kernels: a lane per sample, or per four samples on aligned dwords (AConvSplit); one instance per container (AKind) ---------------
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_pre (AConvPlan p, const uint8_t *__restrict__ in, uint8_t *__restrict__ mid, AConvSplit s)
 {
-  const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= frames * (size_t) p.out_ch)
+  const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= aconv_split_lanes (s))
     return;
-  aconv_pre_sample (p, in, mid, i / (size_t) p.out_ch, (int) (i % (size_t) p.out_ch));
+  aconv_pre_lane<K> (p, in, mid, s, t);
 }
 
+template <int K>
 __global__ __launch_bounds__ (256) void k_aconv_post (AConvPlan p, const AConvJump *__restrict__ jump, AConvDitherState ds, const uint8_t *__restrict__ mid,
-    uint8_t *__restrict__ out, int32_t *__restrict__ qv, int32_t *__restrict__ qd, size_t samples)
+    uint8_t *__restrict__ out, int32_t *__restrict__ qv, int32_t *__restrict__ qd, AConvSplit s)
 {
-  const size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= samples)
+  const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= aconv_split_lanes (s))
     return;
-  aconv_post_sample (p, *jump, ds, mid, out, qv, qd, i);
+  aconv_post_lane<K> (p, *jump, ds, mid, out, qv, qd, s, t);
 }
 
 // noise shaping: the error recurrence of a channel is sequential in time, so one lane walks one channel's frames (the samples and
 // dither words were prepared in parallel by k_aconv_post)
+template <int K>
 __global__ __launch_bounds__ (64) void k_aconv_shape (AConvPlan p, const int32_t *__restrict__ qv, const int32_t *__restrict__ qd, int32_t *__restrict__ hist,
     uint8_t *__restrict__ out, size_t frames)
 {
   const int c = (int) threadIdx.x;
   if (c < p.out_ch)
-    aconv_shape_channel (p, qv, qd, hist, out, frames, c);
+    aconv_shape_channel<K> (p, qv, qd, hist, out, frames, c);
 }
+
+// the endian plan: the samples' bytes reversed (in may be out)
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_swap (const uint8_t *in, uint8_t *out, AConvSplit s)
+{
+  const size_t t = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= aconv_split_lanes (s))
+    return;
+  aconv_swap_lane<K> (in, out, s, t);
+}
+
+static unsigned aconv_blocks (const AConvSplit &s) { return (unsigned) ((aconv_split_lanes (s) + 255) / 256); }
 
 struct GstAmdAudioConverter {
   GstAmdAudioInfo in, out;
@@ -240,6 +255,20 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
   }
   if (!c->resampler && in_frames != out_frames)
     return aconv_fail (GSTAMD_ERR_INVALID, "in_frames != out_frames without a resampler");
+  if (p.endian_swap) {
+    if (!in)
+      return aconv_fail (GSTAMD_ERR_INVALID, "NULL input");
+    const AConvSplit s = aconv_swap_split (in, out, p.endian_swap, out_frames * (size_t) p.out_ch);
+    switch (p.endian_swap) {
+      case 2: k_aconv_swap<AK_2LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
+      case 3: k_aconv_swap<AK_3LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
+      case 4: k_aconv_swap<AK_4LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
+      default: k_aconv_swap<AK_8LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
+    }
+    if (hipGetLastError () != hipSuccess)
+      return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
+    return GSTAMD_OK;
+  }
   const size_t mid_bytes_in = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
   int r;
   const uint8_t *after = nullptr;
@@ -247,8 +276,12 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
     if ((r = ensure (&c->mid_a, &c->mid_a_size, (in_frames ? in_frames : 1) * mid_bytes_in)) != GSTAMD_OK)
       return r;
     const size_t n = in_frames * (size_t) p.out_ch;
-    if (n)
-      hipLaunchKernelGGL (k_aconv_pre, dim3 ((unsigned) ((n + 255) / 256)), dim3 (256), 0, stream, p, (const uint8_t *) in, c->mid_a, in_frames);
+    if (n) {
+      const AConvSplit s = aconv_split (in, afmt_bytes (p.in_fmt), n, aconv_pre_grouped (p));
+#define PRE(K) k_aconv_pre<K><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (p, (const uint8_t *) in, c->mid_a, s)
+      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+    }
     after = c->mid_a;
   } else if (!c->resampler) {
     return aconv_fail (GSTAMD_ERR_INVALID, "NULL input");
@@ -268,10 +301,16 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
     if ((r = ensure (&c->q_v, &c->q_v_size, samples * 4)) != GSTAMD_OK || (r = ensure (&c->q_d, &c->q_d_size, samples * 4)) != GSTAMD_OK)
       return r;
   }
-  hipLaunchKernelGGL (k_aconv_post, dim3 ((unsigned) ((samples + 255) / 256)), dim3 (256), 0, stream, p, c->jump_dev, c->dither, after, (uint8_t *) out,
-      (int32_t *) c->q_v, (int32_t *) c->q_d, samples);
-  if (p.ns && p.quant_shift > 0)
-    hipLaunchKernelGGL (k_aconv_shape, dim3 (1), dim3 (64), 0, stream, p, (const int32_t *) c->q_v, (const int32_t *) c->q_d, c->hist, (uint8_t *) out, out_frames);
+  const AConvSplit s = aconv_split (out, afmt_bytes (p.out_fmt), samples, aconv_post_grouped (p));
+#define POST(K) k_aconv_post<K><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (p, c->jump_dev, c->dither, after, (uint8_t *) out, (int32_t *) c->q_v, \
+    (int32_t *) c->q_d, s)
+  GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+  if (p.ns && p.quant_shift > 0) {
+#define SHAPE(K) k_aconv_shape<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, (const int32_t *) c->q_v, (const int32_t *) c->q_d, c->hist, (uint8_t *) out, out_frames)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+  }
   if (hipGetLastError () != hipSuccess)
     return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
   /* the generator moves on by the draws of this call (setup_dither_buf draws for every sample of the block) */

@@ -28,6 +28,11 @@ enum AMid : int { AMID_S16 = 0, AMID_S32 = 1, AMID_F32 = 2, AMID_F64 = 3 };
 
 struct AConvPlan {
   int in_fmt, out_fmt;          // GSTAMD_AFMT_*
+  int in_kind, out_kind;        // AKind: the containers, which the kernels are instantiated for
+  int in_shift;                 // integer input: 32 - depth
+  uint32_t in_sx;               // integer input: 0x80000000 for the unsigned formats
+  int out_shift, out_usgn;      // integer output: 32 - depth, unsigned
+  int endian_swap;              // the whole conversion is a byte swap of this many bytes per sample (converter_endian); 0: it is not
   int in_ch, out_ch;
   int mid_in;                   // AMid after unpack (+ convert_in): what the mixer and the resampler work on
   int convert_in;               // S32 -> F64 after unpack
@@ -46,16 +51,56 @@ struct AConvPlan {
 };
 
 GSTAMD_AC int amid_bytes (int mid) { return mid == AMID_S16 ? 2 : mid == AMID_F64 ? 8 : 4; }
-GSTAMD_AC int afmt_bytes (int fmt)
+
+// ---- the raw GstAudioFormats, values 2 .. 31 (audio-format.h:80-130) --------------------------------------------------------------------------------
+// Values 4 .. 27 come in groups of four - LE, BE, unsigned LE, unsigned BE - of one container / depth; 28 .. 31 are F32 / F64, LE then BE.
+struct AFmtDesc {
+  bool known, integer, usgn, be;
+  int depth, bytes;
+};
+
+GSTAMD_AC AFmtDesc afmt_desc (int fmt)
 {
-  switch (fmt) {
-    case GSTAMD_AFMT_S8: case GSTAMD_AFMT_U8: return 1;
-    case GSTAMD_AFMT_S16LE: return 2;
-    case GSTAMD_AFMT_S24LE: return 3;
-    case GSTAMD_AFMT_F64LE: return 8;
-    default: return 4;
+  if (fmt == GSTAMD_AFMT_S8 || fmt == GSTAMD_AFMT_U8)
+    return {true, true, fmt == GSTAMD_AFMT_U8, false, 8, 1};
+  if (fmt >= GSTAMD_AFMT_S16LE && fmt <= GSTAMD_AFMT_U18BE) {
+    const int g = (fmt - GSTAMD_AFMT_S16LE) >> 2;               /* S16, S24_32, S32, S24, S20, S18 */
+    const int depth = g == 0 ? 16 : g == 2 ? 32 : g == 4 ? 20 : g == 5 ? 18 : 24;
+    const int bytes = g == 0 ? 2 : g <= 2 ? 4 : 3;
+    return {true, true, (fmt & 2) != 0, (fmt & 1) != 0, depth, bytes};
   }
+  if (fmt >= GSTAMD_AFMT_F32LE && fmt <= GSTAMD_AFMT_F64BE)
+    return {true, false, false, (fmt & 1) != 0, fmt < GSTAMD_AFMT_F64LE ? 32 : 64, fmt < GSTAMD_AFMT_F64LE ? 4 : 8};
+  return {false, false, false, false, 0, 0};
 }
+
+GSTAMD_AC int afmt_bytes (int fmt) { return afmt_desc (fmt).bytes; }
+
+// What a kernel has to know of a format at compile time is its container: bytes per sample and byte order.  Depth and sign are a shift
+// and an xor taken from the plan (uniform over a launch), so the kernels are instantiated per AKind and hold no format switch.
+enum AKind : int { AK_1 = 0, AK_2LE, AK_2BE, AK_3LE, AK_3BE, AK_4LE, AK_4BE, AK_8LE, AK_8BE };
+
+GSTAMD_AC constexpr int akind_bytes (int k) { return k == AK_1 ? 1 : k <= AK_2BE ? 2 : k <= AK_3BE ? 3 : k <= AK_4BE ? 4 : 8; }
+GSTAMD_AC constexpr bool akind_be (int k) { return k == AK_2BE || k == AK_3BE || k == AK_4BE || k == AK_8BE; }
+GSTAMD_AC int afmt_kind (int fmt)
+{
+  const AFmtDesc d = afmt_desc (fmt);
+  return d.bytes == 1 ? AK_1 : (d.bytes == 2 ? AK_2LE : d.bytes == 3 ? AK_3LE : d.bytes == 4 ? AK_4LE : AK_8LE) + (d.be ? 1 : 0);
+}
+
+// the switch outside the loop: F (K) with the container as a constant
+#define GSTAMD_ACONV_FOR_KIND(kind, F) \
+  switch (kind) { \
+    case gstamd::AK_1: F (gstamd::AK_1); break; \
+    case gstamd::AK_2LE: F (gstamd::AK_2LE); break; \
+    case gstamd::AK_2BE: F (gstamd::AK_2BE); break; \
+    case gstamd::AK_3LE: F (gstamd::AK_3LE); break; \
+    case gstamd::AK_3BE: F (gstamd::AK_3BE); break; \
+    case gstamd::AK_4LE: F (gstamd::AK_4LE); break; \
+    case gstamd::AK_4BE: F (gstamd::AK_4BE); break; \
+    case gstamd::AK_8LE: F (gstamd::AK_8LE); break; \
+    default: F (gstamd::AK_8BE); break; \
+  }
 
 // ORC's C backups flush denormals around float operations (ORC_DENORMAL / ORC_DENORMAL_DOUBLE, orc/orcprogram-c.c): a value whose
 // exponent field is zero keeps only its sign
@@ -66,62 +111,234 @@ GSTAMD_AC uint64_t d_bits (double d) { uint64_t b; memcpy (&b, &d, 8); return b;
 GSTAMD_AC float bits_f (uint32_t b) { float f; memcpy (&f, &b, 4); return f; }
 GSTAMD_AC uint32_t f_bits (float f) { uint32_t b; memcpy (&b, &f, 4); return b; }
 
-// sample i of a buffer in `fmt`, unpacked to S32 (integer formats)
-GSTAMD_AC int32_t aconv_unpack_int (const uint8_t *p, int fmt, size_t i)
+// v_perm_b32: result byte i is the byte the selector's byte i names - 0 .. 3 of lo, 4 .. 7 of hi, 0x0c a zero byte
+GSTAMD_AC uint32_t aconv_perm (uint32_t hi, uint32_t lo, uint32_t sel)
 {
-  switch (fmt) {
-    /* do_unpack passes GST_AUDIO_PACK_FLAG_TRUNCATE_RANGE (audio-converter.c:477): the *_trunc programs, plain shifts */
-    case GSTAMD_AFMT_S8: return (int32_t) ((uint32_t) p[i] << 24);                                  // splatbl, shll 24
-    case GSTAMD_AFMT_U8: return (int32_t) (((uint32_t) p[i] << 24) ^ 0x80000000u);
-    case GSTAMD_AFMT_S16LE: {
-      const uint32_t s = (uint32_t) p[2 * i] | ((uint32_t) p[2 * i + 1] << 8);
-      return (int32_t) (s << 16);                                                                   // convuwl, shll 16
-    }
-    case GSTAMD_AFMT_S24LE:
-      return (int32_t) (((uint32_t) p[3 * i] | ((uint32_t) p[3 * i + 1] << 8) | ((uint32_t) p[3 * i + 2] << 16)) << 8);
-    case GSTAMD_AFMT_S24_32LE: {
-      uint32_t v; memcpy (&v, p + 4 * i, 4);
-      return (int32_t) (v << 8);
-    }
-    default: {
-      int32_t v; memcpy (&v, p + 4 * i, 4);
-      return v;
-    }
+#ifdef __HIP_DEVICE_COMPILE__
+  return __builtin_amdgcn_perm (hi, lo, sel);
+#else                           /* the plain C twin: the host emulator of tests/emu, and the host pass of hipcc */
+  const uint64_t both = ((uint64_t) hi << 32) | lo;
+  uint32_t r = 0;
+  for (int i = 0; i < 4; i++) {
+    const uint32_t s = (sel >> (8 * i)) & 0xffu;
+    r |= (s < 8 ? (uint32_t) (both >> (8 * s)) & 0xffu : 0u) << (8 * i);
   }
+  return r;
+#endif
 }
+GSTAMD_AC uint32_t aconv_bswap32 (uint32_t v) { return aconv_perm (0u, v, 0x00010203u); }
+GSTAMD_AC uint64_t aconv_bswap64 (uint64_t v) { return ((uint64_t) aconv_bswap32 ((uint32_t) v) << 32) | aconv_bswap32 ((uint32_t) (v >> 32)); }
 
-// sample i of a float buffer, unpacked to F64 (audio_orc_unpack_f32: convfd with the denormal flush; f64: a copy)
-GSTAMD_AC double aconv_unpack_flt (const uint8_t *p, int fmt, size_t i)
+// ---- one sample: the container as an unsigned word in the format's byte order, read and written byte-wise (any address) ---------------
+template <int K> GSTAMD_AC uint32_t aconv_load_w (const uint8_t *p, size_t i)
 {
-  if (fmt == GSTAMD_AFMT_F32LE) {
-    uint32_t b; memcpy (&b, p + 4 * i, 4);
-    return (double) bits_f (orc_denormal_f (b));
-  }
-  double d; memcpy (&d, p + 8 * i, 8);
-  return d;
-}
-
-GSTAMD_AC void aconv_pack_int (uint8_t *p, int fmt, size_t i, int32_t v)
-{
-  switch (fmt) {
-    case GSTAMD_AFMT_S8: p[i] = (uint8_t) ((uint32_t) v >> 24); break;
-    case GSTAMD_AFMT_U8: p[i] = (uint8_t) (((uint32_t) v ^ 0x80000000u) >> 24); break;
-    case GSTAMD_AFMT_S16LE: { const uint16_t h = (uint16_t) ((uint32_t) v >> 16); memcpy (p + 2 * i, &h, 2); break; }
-    case GSTAMD_AFMT_S24LE: { const uint32_t t = (uint32_t) (v >> 8); p[3 * i] = (uint8_t) t; p[3 * i + 1] = (uint8_t) (t >> 8); p[3 * i + 2] = (uint8_t) (t >> 16); break; }
-    case GSTAMD_AFMT_S24_32LE: { const int32_t t = v >> 8; memcpy (p + 4 * i, &t, 4); break; }
-    default: memcpy (p + 4 * i, &v, 4); break;
-  }
-}
-
-GSTAMD_AC void aconv_pack_flt (uint8_t *p, int fmt, size_t i, double v)
-{
-  if (fmt == GSTAMD_AFMT_F32LE) {               // audio_orc_pack_f32: convdf, denormals flushed on both sides
-    const float f = (float) bits_d (orc_denormal_d (d_bits (v)));
-    const uint32_t b = orc_denormal_f (f_bits (f));
-    memcpy (p + 4 * i, &b, 4);
+  constexpr int B = akind_bytes (K);
+  const uint8_t *q = p + (size_t) B * i;
+  if constexpr (B == 1) {
+    return q[0];
+  } else if constexpr (B == 2) {
+    return akind_be (K) ? ((uint32_t) q[0] << 8) | q[1] : (uint32_t) q[0] | ((uint32_t) q[1] << 8);
+  } else if constexpr (B == 3) {
+    return akind_be (K) ? ((uint32_t) q[0] << 16) | ((uint32_t) q[1] << 8) | q[2] : (uint32_t) q[0] | ((uint32_t) q[1] << 8) | ((uint32_t) q[2] << 16);
   } else {
-    memcpy (p + 8 * i, &v, 8);
+    uint32_t v; memcpy (&v, q, 4);
+    return akind_be (K) ? aconv_bswap32 (v) : v;
   }
+}
+
+template <int K> GSTAMD_AC uint64_t aconv_load_w64 (const uint8_t *p, size_t i)
+{
+  uint64_t v; memcpy (&v, p + 8 * i, 8);
+  return akind_be (K) ? aconv_bswap64 (v) : v;
+}
+
+template <int K> GSTAMD_AC void aconv_store_w (uint8_t *p, size_t i, uint32_t t)
+{
+  constexpr int B = akind_bytes (K);
+  uint8_t *q = p + (size_t) B * i;
+  if constexpr (B == 1) {
+    q[0] = (uint8_t) t;
+  } else if constexpr (B == 2) {
+    q[akind_be (K) ? 1 : 0] = (uint8_t) t; q[akind_be (K) ? 0 : 1] = (uint8_t) (t >> 8);
+  } else if constexpr (B == 3) {
+    q[akind_be (K) ? 2 : 0] = (uint8_t) t; q[1] = (uint8_t) (t >> 8); q[akind_be (K) ? 0 : 2] = (uint8_t) (t >> 16);
+  } else {
+    const uint32_t v = akind_be (K) ? aconv_bswap32 (t) : t;
+    memcpy (q, &v, 4);
+  }
+}
+
+template <int K> GSTAMD_AC void aconv_store_w64 (uint8_t *p, size_t i, uint64_t t)
+{
+  const uint64_t v = akind_be (K) ? aconv_bswap64 (t) : t;
+  memcpy (p + 8 * i, &v, 8);
+}
+
+// N dwords at a 4-byte aligned address (consecutive dword accesses of a lane become one global_load / _store_dwordxN)
+typedef uint32_t __attribute__ ((may_alias)) aconv_u32;
+template <int N> GSTAMD_AC void aconv_load_words (const void *q, uint32_t *d)
+{
+  const aconv_u32 *s = (const aconv_u32 *) q;
+  for (int j = 0; j < N; j++)
+    d[j] = s[j];
+}
+
+template <int N> GSTAMD_AC void aconv_store_words (void *q, const uint32_t *d)
+{
+  aconv_u32 *s = (aconv_u32 *) q;
+  for (int j = 0; j < N; j++)
+    s[j] = d[j];
+}
+
+// ---- four consecutive samples on aligned dwords: 4 samples of a B-byte container are B dwords; q is 4-byte aligned ---------------------
+template <int K> GSTAMD_AC void aconv_load4 (const uint8_t *q, uint32_t w[4])
+{
+  constexpr int B = akind_bytes (K);
+  constexpr bool BE = akind_be (K);
+  static_assert (B <= 4, "64-bit containers: aconv_load4_64");
+  uint32_t d[B];
+  aconv_load_words<B> (q, d);
+  if constexpr (B == 1) {
+    for (int j = 0; j < 4; j++)
+      w[j] = (d[0] >> (8 * j)) & 0xffu;
+  } else if constexpr (B == 2) {
+    for (int j = 0; j < 2; j++) {
+      w[2 * j] = BE ? aconv_perm (0u, d[j], 0x0c0c0001u) : d[j] & 0xffffu;
+      w[2 * j + 1] = BE ? aconv_perm (0u, d[j], 0x0c0c0203u) : d[j] >> 16;
+    }
+  } else if constexpr (B == 3) {        /* stream bytes 0 .. 11 = d[0] d[1] d[2]; sample j is bytes 3j .. 3j + 2 */
+    w[0] = aconv_perm (0u, d[0], BE ? 0x0c000102u : 0x0c020100u);
+    w[1] = aconv_perm (d[1], d[0], BE ? 0x0c030405u : 0x0c050403u);
+    w[2] = aconv_perm (d[2], d[1], BE ? 0x0c020304u : 0x0c040302u);
+    w[3] = aconv_perm (0u, d[2], BE ? 0x0c010203u : 0x0c030201u);
+  } else {
+    for (int j = 0; j < 4; j++)
+      w[j] = BE ? aconv_bswap32 (d[j]) : d[j];
+  }
+}
+
+template <int K> GSTAMD_AC void aconv_store4 (uint8_t *q, const uint32_t t[4])
+{
+  constexpr int B = akind_bytes (K);
+  constexpr bool BE = akind_be (K);
+  static_assert (B <= 4, "64-bit containers: aconv_store4_64");
+  uint32_t d[B];
+  if constexpr (B == 1) {
+    d[0] = aconv_perm (t[1], t[0], 0x0c0c0400u) | aconv_perm (t[3], t[2], 0x04000c0cu);
+  } else if constexpr (B == 2) {
+    d[0] = aconv_perm (t[1], t[0], BE ? 0x04050001u : 0x05040100u);
+    d[1] = aconv_perm (t[3], t[2], BE ? 0x04050001u : 0x05040100u);
+  } else if constexpr (B == 3) {
+    d[0] = aconv_perm (t[1], t[0], BE ? 0x06000102u : 0x04020100u);
+    d[1] = aconv_perm (t[2], t[1], BE ? 0x05060001u : 0x05040201u);
+    d[2] = aconv_perm (t[3], t[2], BE ? 0x04050600u : 0x06050402u);
+  } else {
+    for (int j = 0; j < 4; j++)
+      d[j] = BE ? aconv_bswap32 (t[j]) : t[j];
+  }
+  aconv_store_words<B> (q, d);
+}
+
+template <int K> GSTAMD_AC void aconv_load4_64 (const uint8_t *q, uint64_t w[4])
+{
+  uint32_t d[8];
+  aconv_load_words<8> (q, d);
+  for (int j = 0; j < 4; j++)
+    w[j] = akind_be (K) ? ((uint64_t) aconv_bswap32 (d[2 * j]) << 32) | aconv_bswap32 (d[2 * j + 1]) : ((uint64_t) d[2 * j + 1] << 32) | d[2 * j];
+}
+
+template <int K> GSTAMD_AC void aconv_store4_64 (uint8_t *q, const uint64_t t[4])
+{
+  uint32_t d[8];
+  for (int j = 0; j < 4; j++) {
+    const uint32_t lo = (uint32_t) t[j], hi = (uint32_t) (t[j] >> 32);
+    d[2 * j] = akind_be (K) ? aconv_bswap32 (hi) : lo;
+    d[2 * j + 1] = akind_be (K) ? aconv_bswap32 (lo) : hi;
+  }
+  aconv_store_words<8> (q, d);
+}
+
+// How the lanes of a launch share n consecutive samples of a caller's buffer: `head` single samples up to the first dword boundary on
+// which a sample starts, then `groups` lanes of four samples on aligned dwords, the rest single again.  groups == 0: a lane per sample.
+struct AConvSplit {
+  size_t head, groups, n;
+};
+
+inline AConvSplit aconv_split (const void *buf, int bytes, size_t n, bool grouped)
+{
+  AConvSplit s = { 0, 0, n };
+  size_t h = 0;
+  while (h < 4 && (((uintptr_t) buf + (size_t) bytes * h) & 3u))
+    h++;
+  if (!grouped || h == 4 || n < h + 4)          /* h == 4: no sample of this buffer starts on a dword */
+    return s;
+  s.head = h;
+  s.groups = (n - h) / 4;
+  return s;
+}
+
+GSTAMD_AC size_t aconv_split_lanes (const AConvSplit &s) { return s.groups + (s.n - 4 * s.groups); }
+// lane t >= groups: the single sample it takes
+GSTAMD_AC size_t aconv_split_single (const AConvSplit &s, size_t t)
+{
+  const size_t k = t - s.groups;
+  return k < s.head ? k : k + 4 * s.groups;
+}
+
+// ---- unpack / pack (audio-format.c unpack_* / pack_*, gstaudiopack.orc) ------------------------------------------------------------------
+// do_unpack passes GST_AUDIO_PACK_FLAG_TRUNCATE_RANGE (audio-converter.c:477): the *_trunc programs, plain shifts.  Integer container w
+// of depth d -> S32: w << (32 - d), sign bit flipped for the unsigned formats; container bits above the depth fall off the top.
+GSTAMD_AC int32_t aconv_w_to_s32 (const AConvPlan &p, uint32_t w) { return (int32_t) ((w << p.in_shift) ^ p.in_sx); }
+
+// S32 -> container: signed formats shift arithmetically (the spare bits of S24_32 / S20 / S18 carry the sign), unsigned ones flip the
+// sign bit and shift logically (spare bits zero)
+GSTAMD_AC uint32_t aconv_s32_to_w (const AConvPlan &p, int32_t v)
+{
+  return p.out_usgn ? ((uint32_t) v ^ 0x80000000u) >> p.out_shift : (uint32_t) (v >> p.out_shift);
+}
+
+// audio_orc_unpack_f32: convfd with the denormal flush; f64: a copy
+GSTAMD_AC double aconv_f32w_to_double (uint32_t b) { return (double) bits_f (orc_denormal_f (b)); }
+
+// audio_orc_pack_f32: convdf, denormals flushed on both sides
+GSTAMD_AC uint32_t aconv_double_to_f32w (double v)
+{
+  const float f = (float) bits_d (orc_denormal_d (d_bits (v)));
+  return orc_denormal_f (f_bits (f));
+}
+
+// sample i of a buffer of container K, unpacked to S32 (integer formats)
+template <int K> GSTAMD_AC int32_t aconv_unpack_int (const AConvPlan &p, const uint8_t *in, size_t i)
+{
+  if constexpr (akind_bytes (K) <= 4)
+    return aconv_w_to_s32 (p, aconv_load_w<K> (in, i));
+  else
+    return 0;
+}
+
+// sample i of a float buffer, unpacked to F64
+template <int K> GSTAMD_AC double aconv_unpack_flt (const uint8_t *in, size_t i)
+{
+  if constexpr (akind_bytes (K) == 4)
+    return aconv_f32w_to_double (aconv_load_w<K> (in, i));
+  else if constexpr (akind_bytes (K) == 8)
+    return bits_d (aconv_load_w64<K> (in, i));
+  else
+    return 0.0;
+}
+
+template <int K> GSTAMD_AC void aconv_pack_int (const AConvPlan &p, uint8_t *out, size_t i, int32_t v)
+{
+  if constexpr (akind_bytes (K) <= 4)
+    aconv_store_w<K> (out, i, aconv_s32_to_w (p, v));
+}
+
+template <int K> GSTAMD_AC void aconv_pack_flt (uint8_t *out, size_t i, double v)
+{
+  if constexpr (akind_bytes (K) == 4)
+    aconv_store_w<K> (out, i, aconv_double_to_f32w (v));
+  else if constexpr (akind_bytes (K) == 8)
+    aconv_store_w64<K> (out, i, d_bits (v));
 }
 
 // audio_orc_s32_to_double: convld, divd 2147483648.0
@@ -272,13 +489,11 @@ GSTAMD_AC int32_t aconv_quantize (const AConvPlan &p, int32_t d, int32_t v)
   return (int32_t) ((uint32_t) aconv_addssl (v, d) & mask);
 }
 
-GSTAMD_AC void aconv_pack_int (uint8_t *p, int fmt, size_t i, int32_t v);
-
 // quantize stage with noise shaping for channel c of a call: the error recurrence runs down the frames (one lane per channel).
 // v / d: the call's S32 samples and dither words; hist: [8][channels] error history carried between calls (zeros after new / reset).
 //   gst_audio_quantize_quantize_int_dither_feedback      audio-quantize.c:199-231
 //   gst_audio_quantize_quantize_int_dither_noise_shape   audio-quantize.c:239-278
-GSTAMD_AC void aconv_shape_channel (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, uint8_t *out, size_t frames, int c)
+template <int K> GSTAMD_AC void aconv_shape_channel (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, uint8_t *out, size_t frames, int c)
 {
   const size_t ch = (size_t) p.out_ch;
   const uint32_t mask = ~((1u << p.quant_shift) - 1u);
@@ -290,7 +505,7 @@ GSTAMD_AC void aconv_shape_channel (const AConvPlan &p, const int32_t *v, const 
       const int32_t err = (int32_t) ((uint32_t) d[i] - e);
       const int32_t x = (int32_t) ((uint32_t) aconv_addssl (o, err) & mask);
       e += (uint32_t) x - (uint32_t) o;
-      aconv_pack_int (out, p.out_fmt, i, x);
+      aconv_pack_int<K> (p, out, i, x);
     }
     hist[c] = (int32_t) e;
     return;
@@ -312,14 +527,14 @@ GSTAMD_AC void aconv_shape_channel (const AConvPlan &p, const int32_t *v, const 
       if (j + 1 < p.n_coeffs)
         h[j] = h[j + 1];
     h[p.n_coeffs - 1] = (uint32_t) ne;
-    aconv_pack_int (out, p.out_fmt, i, x);
+    aconv_pack_int<K> (p, out, i, x);
   }
   for (int j = 0; j < p.n_coeffs; j++)
     hist[(size_t) j * ch + (size_t) c] = (int32_t) h[j];
 }
 
 // ---- stage 1: input frame n, output channel co -> one sample in the mid_in format ------------------------------------------------
-GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t *mid, size_t n, int co)
+template <int K> GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t *mid, size_t n, int co)
 {
   const size_t o = n * (size_t) p.out_ch + (size_t) co;
   const size_t ibase = n * (size_t) p.in_ch;
@@ -347,12 +562,12 @@ GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t 
     case AMID_S32: {
       int32_t r;
       if (!p.mix) {
-        r = aconv_unpack_int (in, p.in_fmt, ibase + co);
+        r = aconv_unpack_int<K> (p, in, ibase + co);
       } else {
         int64_t res = 0;
         for (int ci = 0; ci < p.in_ch; ci++)
           if ((p.use[co] >> ci) & 1u)
-            res += (int64_t) aconv_unpack_int (in, p.in_fmt, ibase + ci) * (int64_t) p.mi[ci][co];
+            res += (int64_t) aconv_unpack_int<K> (p, in, ibase + ci) * (int64_t) p.mi[ci][co];
         res = (res + 512) >> 10;
         r = res > 2147483647ll ? 2147483647 : (res < -2147483648ll ? (int32_t) 0x80000000u : (int32_t) res);
       }
@@ -378,13 +593,13 @@ GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t 
     default: {
       double r;
       if (!p.mix) {
-        r = p.convert_in ? aconv_s32_to_double (aconv_unpack_int (in, p.in_fmt, ibase + co)) : aconv_unpack_flt (in, p.in_fmt, ibase + co);
+        r = p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, in, ibase + co)) : aconv_unpack_flt<K> (in, ibase + co);
       } else {
         r = 0.0;
         for (int ci = 0; ci < p.in_ch; ci++) {
           if (!((p.use[co] >> ci) & 1u))
             continue;
-          const double v = p.convert_in ? aconv_s32_to_double (aconv_unpack_int (in, p.in_fmt, ibase + ci)) : aconv_unpack_flt (in, p.in_fmt, ibase + ci);
+          const double v = p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, in, ibase + ci)) : aconv_unpack_flt<K> (in, ibase + ci);
           r += v * p.m[ci][co];
         }
       }
@@ -394,10 +609,72 @@ GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t 
   }
 }
 
+// a lane of the first kernel.  Without a mix, output sample i is input sample i, and a lane of the grouped part takes four of them:
+// B dwords of the caller's buffer in, 4 (S32) or 8 (F64) dwords of the mid buffer out.
+template <int K> GSTAMD_AC void aconv_pre_lane (const AConvPlan &p, const uint8_t *in, uint8_t *mid, const AConvSplit &s, size_t t)
+{
+  if (t >= s.groups) {
+    const size_t i = aconv_split_single (s, t);
+    aconv_pre_sample<K> (p, in, mid, i / (size_t) p.out_ch, (int) (i % (size_t) p.out_ch));
+    return;
+  }
+  constexpr int B = akind_bytes (K);
+  const size_t i = s.head + 4 * t;
+  const uint8_t *q = in + (size_t) B * i;
+  if (p.mid_in == AMID_S32) {
+    if constexpr (B <= 4) {
+      uint32_t w[4];
+      uint32_t r[4];
+      aconv_load4<K> (q, w);
+      for (int j = 0; j < 4; j++)
+        r[j] = (uint32_t) aconv_w_to_s32 (p, w[j]);
+      aconv_store_words<4> (mid + 4 * i, r);
+    }
+    return;
+  }
+  double r[4];
+  if constexpr (B <= 4) {
+    uint32_t w[4];
+    aconv_load4<K> (q, w);
+    for (int j = 0; j < 4; j++)
+      r[j] = p.convert_in ? aconv_s32_to_double (aconv_w_to_s32 (p, w[j])) : aconv_f32w_to_double (w[j]);
+  } else {
+    uint64_t w[4];
+    aconv_load4_64<K> (q, w);
+    for (int j = 0; j < 4; j++)
+      r[j] = bits_d (w[j]);
+  }
+  uint32_t rw[8];
+  memcpy (rw, r, 32);
+  aconv_store_words<8> (mid + 8 * i, rw);
+}
+
+// the first kernel's lanes can take four samples each: no mix (so no gather over the input channels), S32 or F64 behind it
+GSTAMD_AC bool aconv_pre_grouped (const AConvPlan &p) { return !p.mix && (p.mid_in == AMID_S32 || p.mid_in == AMID_F64); }
+GSTAMD_AC bool aconv_post_grouped (const AConvPlan &p) { return p.mid_in == AMID_S32 || p.mid_in == AMID_F64; }
+
 // ---- stage 2: sample i (interleaved index) of the mid buffer after the resampler -> the output format -----------------------------
-// With noise shaping (p.ns) the sample and its dither word go to qv / qd for aconv_shape_channel instead.
-GSTAMD_AC void aconv_post_sample (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, int32_t *qv, int32_t *qd,
-    size_t i)
+// convert_out and the quantize stage without noise shaping: the S32 sample that is packed.  With noise shaping (returns true) the
+// sample and its dither word are for aconv_shape_channel instead.
+GSTAMD_AC bool aconv_post_int (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, size_t i, int32_t *v, int32_t *d)
+{
+  if (p.convert_out) {
+    double x; memcpy (&x, mid + 8 * i, 8);
+    *v = aconv_double_to_s32 (x);
+  } else {
+    memcpy (v, mid + 4 * i, 4);
+  }
+  if (p.quant_shift > 0) {
+    *d = aconv_dither_value (p, jump, ds, i);
+    if (p.ns)
+      return true;
+    *v = aconv_quantize (p, *d, *v);
+  }
+  return false;
+}
+
+template <int K> GSTAMD_AC void aconv_post_sample (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, int32_t *qv,
+    int32_t *qd, size_t i)
 {
   if (p.mid_in == AMID_S16) {
     memcpy (out + 2 * i, mid + 2 * i, 2);
@@ -409,26 +686,132 @@ GSTAMD_AC void aconv_post_sample (const AConvPlan &p, const AConvJump &jump, con
   }
   if (p.mid_out == AMID_F64) {
     double v; memcpy (&v, mid + 8 * i, 8);
-    aconv_pack_flt (out, p.out_fmt, i, v);
+    aconv_pack_flt<K> (out, i, v);
     return;
   }
-  int32_t v;
-  if (p.convert_out) {
-    double d; memcpy (&d, mid + 8 * i, 8);
-    v = aconv_double_to_s32 (d);
-  } else {
-    memcpy (&v, mid + 4 * i, 4);
+  int32_t v, d = 0;
+  if (aconv_post_int (p, jump, ds, mid, i, &v, &d)) {
+    qv[i] = v;
+    qd[i] = d;
+    return;
   }
-  if (p.quant_shift > 0) {
-    const int32_t d = aconv_dither_value (p, jump, ds, i);
-    if (p.ns) {
-      qv[i] = v;
-      qd[i] = d;
+  aconv_pack_int<K> (p, out, i, v);
+}
+
+// a lane of the second kernel; a lane of the grouped part writes four samples as B dwords of the caller's buffer
+template <int K> GSTAMD_AC void aconv_post_lane (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, int32_t *qv,
+    int32_t *qd, const AConvSplit &s, size_t t)
+{
+  if (t >= s.groups) {
+    aconv_post_sample<K> (p, jump, ds, mid, out, qv, qd, aconv_split_single (s, t));
+    return;
+  }
+  constexpr int B = akind_bytes (K);
+  const size_t i = s.head + 4 * t;
+  uint8_t *q = out + (size_t) B * i;
+  if (p.mid_out == AMID_F64) {
+    double v[4];
+    uint32_t vw[8];
+    aconv_load_words<8> (mid + 8 * i, vw);
+    memcpy (v, vw, 32);
+    if constexpr (B == 4) {
+      uint32_t w[4];
+      for (int j = 0; j < 4; j++)
+        w[j] = aconv_double_to_f32w (v[j]);
+      aconv_store4<K> (q, w);
+    } else if constexpr (B == 8) {
+      uint64_t w[4];
+      for (int j = 0; j < 4; j++)
+        w[j] = d_bits (v[j]);
+      aconv_store4_64<K> (q, w);
+    }
+    return;
+  }
+  if constexpr (B <= 4) {
+    int32_t v[4], d[4] = { 0, 0, 0, 0 };
+    bool shaped = false;
+    for (int j = 0; j < 4; j++)
+      shaped = aconv_post_int (p, jump, ds, mid, i + (size_t) j, &v[j], &d[j]);       /* (uniform over the launch) */
+    if (shaped) {
+      for (int j = 0; j < 4; j++) {
+        qv[i + (size_t) j] = v[j];
+        qd[i + (size_t) j] = d[j];
+      }
       return;
     }
-    v = aconv_quantize (p, d, v);
+    uint32_t w[4];
+    for (int j = 0; j < 4; j++)
+      w[j] = aconv_s32_to_w (p, v[j]);
+    aconv_store4<K> (q, w);
   }
-  aconv_pack_int (out, p.out_fmt, i, v);
 }
+
+// ---- the endian plan (converter_endian): every sample's bytes reversed, nothing else.  K is the little-endian container of the width;
+// reading it as LE and writing it as BE is the swap in either direction.  in == out is fine: a lane reads its bytes before it writes them.
+template <int K> GSTAMD_AC void aconv_swap_lane (const uint8_t *in, uint8_t *out, const AConvSplit &s, size_t t)
+{
+  constexpr int B = akind_bytes (K);
+  if (t >= s.groups) {
+    const size_t i = aconv_split_single (s, t);
+    if constexpr (B == 8)
+      aconv_store_w64<K + 1> (out, i, aconv_load_w64<K> (in, i));
+    else
+      aconv_store_w<K + 1> (out, i, aconv_load_w<K> (in, i));
+    return;
+  }
+  const size_t i = s.head + 4 * t;
+  if constexpr (B == 8) {
+    uint64_t w[4];
+    aconv_load4_64<K> (in + 8 * i, w);
+    aconv_store4_64<K + 1> (out + 8 * i, w);
+  } else {
+    uint32_t w[4];
+    aconv_load4<K> (in + (size_t) B * i, w);
+    aconv_store4<K + 1> (out + (size_t) B * i, w);
+  }
+}
+
+// the lanes of a swap: grouped where the two buffers reach a dword boundary at the same sample
+inline AConvSplit aconv_swap_split (const void *in, const void *out, int bytes, size_t n)
+{
+  return aconv_split (in, bytes, n, (((uintptr_t) in ^ (uintptr_t) out) & 3u) == 0);
+}
+
+#ifndef __HIPCC__
+// ---- one sample at a time with the container looked up per call: the entry points of a host loop that walks samples, not lanes
+// (tests/emu/emu_audio.cpp).  The kernels never come here.  For the endian plan the first stage parks the container in the sample's mid
+// slot (which is at least as wide) and the second one writes it out reversed.
+inline void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t *mid, size_t n, int co)
+{
+  if (p.endian_swap) {
+    const size_t i = n * (size_t) p.out_ch + (size_t) co;
+    memcpy (mid + (size_t) amid_bytes (p.mid_in) * i, in + (size_t) p.endian_swap * i, (size_t) p.endian_swap);
+    return;
+  }
+#define GSTAMD_ACONV_F(K) aconv_pre_sample<K> (p, in, mid, n, co)
+  GSTAMD_ACONV_FOR_KIND (p.in_kind, GSTAMD_ACONV_F);
+#undef GSTAMD_ACONV_F
+}
+
+inline void aconv_post_sample (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, int32_t *qv, int32_t *qd, size_t i)
+{
+  if (p.endian_swap) {
+    const uint8_t *q = mid + (size_t) amid_bytes (p.mid_in) * i;
+    for (int b = 0; b < p.endian_swap; b++)
+      out[(size_t) p.endian_swap * i + (size_t) b] = q[p.endian_swap - 1 - b];
+    return;
+  }
+#define GSTAMD_ACONV_F(K) aconv_post_sample<K> (p, jump, ds, mid, out, qv, qd, i)
+  GSTAMD_ACONV_FOR_KIND (p.out_kind, GSTAMD_ACONV_F);
+#undef GSTAMD_ACONV_F
+}
+
+inline void aconv_shape_channel (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, uint8_t *out, size_t frames, int c)
+{
+#define GSTAMD_ACONV_F(K) aconv_shape_channel<K> (p, v, d, hist, out, frames, c)
+  GSTAMD_ACONV_FOR_KIND (p.out_kind, GSTAMD_ACONV_F);
+#undef GSTAMD_ACONV_F
+}
+#endif
 
 }  // namespace gstamd

@@ -18,15 +18,15 @@ struct AFmtInfo {
 
 static AFmtInfo afmt_info (int fmt)
 {
-  switch (fmt) {
-    case GSTAMD_AFMT_S8: case GSTAMD_AFMT_U8: return {true, true, 8};
-    case GSTAMD_AFMT_S16LE: return {true, true, 16};
-    case GSTAMD_AFMT_S24LE: case GSTAMD_AFMT_S24_32LE: return {true, true, 24};
-    case GSTAMD_AFMT_S32LE: return {true, true, 32};
-    case GSTAMD_AFMT_F32LE: return {true, false, 32};
-    case GSTAMD_AFMT_F64LE: return {true, false, 64};
-    default: return {false, false, 0};
-  }
+  const AFmtDesc d = afmt_desc (fmt);
+  return {d.known, d.integer, d.depth};
+}
+
+// the same format apart from the byte order (S16LE / S16BE, U20LE / U20BE, F64LE / F64BE ...)
+static bool afmt_endian_pair (int a, int b)
+{
+  const AFmtDesc x = afmt_desc (a), y = afmt_desc (b);
+  return x.known && y.known && x.integer == y.integer && x.usgn == y.usgn && x.depth == y.depth && x.bytes == y.bytes && x.be != y.be;
 }
 
 static bool afmt_is_intermediate (int fmt)
@@ -248,13 +248,13 @@ static void default_mix_matrix (const GstAmdAudioInfo &in, const GstAmdAudioInfo
 }
 
 // The whole plan.  *resample: a resampler (on p->mid_in, out->channels) sits between the two kernels; *passthrough: the bytes
-// themselves.  Returns GSTAMD_OK or an error code with *err set.
+// themselves; plan->endian_swap: the bytes of every sample reversed.  Returns GSTAMD_OK or an error code with *err set.
 inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAudioInfo *out, const GstAmdAudioConverterConfig &cfg, AConvPlan *plan,
     bool *resample, bool *passthrough, std::string *err)
 {
   const AFmtInfo fi = afmt_info (in->format), fo = afmt_info (out->format);
   if (!fi.known || !fo.known) {
-    *err = "sample format not built on the GPU path (S8, U8, S16LE, S24LE, S24_32LE, S32LE, F32LE, F64LE are)";
+    *err = "not a raw sample format (GstAudioFormat 2 .. 31: S8 / U8, S16 / S24_32 / S32 / S24 / S20 / S18 signed and unsigned, F32 / F64, either byte order)";
     return GSTAMD_ERR_UNSUPPORTED;
   }
   if (in->channels < 1 || out->channels < 1 || in->channels > GSTAMD_AUDIO_MAX_CHANNELS || out->channels > GSTAMD_AUDIO_MAX_CHANNELS) {
@@ -280,6 +280,15 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
   p.out_fmt = out->format;
   p.in_ch = in->channels;
   p.out_ch = out->channels;
+  {
+    const AFmtDesc di = afmt_desc (in->format), dout = afmt_desc (out->format);
+    p.in_kind = afmt_kind (in->format);
+    p.out_kind = afmt_kind (out->format);
+    p.in_shift = di.integer ? 32 - di.depth : 0;
+    p.in_sx = di.integer && di.usgn ? 0x80000000u : 0u;
+    p.out_shift = dout.integer ? 32 - dout.depth : 0;
+    p.out_usgn = dout.integer && dout.usgn ? 1 : 0;
+  }
   /* chain_unpack :708-740 */
   const bool same_format = in->format == out->format;
   int cur = (same_format && afmt_is_intermediate (in->format)) ? afmt_mid (in->format) : (fi.integer ? AMID_S32 : AMID_F64);
@@ -362,6 +371,12 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
   }
   /* "optimize" :1404-1453: same format, passthrough mixing, no resampler -> the bytes themselves */
   *passthrough = mix_passthrough && same_format && !*resample;
+  /* the same, with formats that differ in byte order only: converter_endian, a byte swap of the samples as they are - no unpack, no
+     quantize (so no dither), and floats are not looked at (denormals and NaN payloads pass) */
+  if (mix_passthrough && !*resample && afmt_endian_pair (in->format, out->format)) {
+    p.endian_swap = afmt_bytes (in->format);
+    p.quant_shift = p.dither = p.ns = p.n_coeffs = 0;           /* this chain has no quantizer */
+  }
   return GSTAMD_OK;
 }
 

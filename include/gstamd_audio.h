@@ -119,10 +119,19 @@ long gstamd_audio_resampler_debug_taps (GstAmdAudioResampler *resampler, double 
 /* ---- GstAudioConverter (gst-libs/gst/audio/audio-converter.h:85-140, audio-converter.c) ------------------------------------------
  * The stages of gst_audio_converter_new's chain (audio-converter.c:708-1090) on the device: unpack -> S32 / F64, S32 -> F64
  * (convert_in), channel mix, resample, F64 -> S32 (convert_out), quantize (dither), pack.  Formats are GstAudioFormat values
- * (audio-format.h:80-130, little-endian ones): */
+ * (audio-format.h:80-130) - all 31 raw ones: S8 / U8; S16, S24_32 (24 bits in 4 bytes), S32, S24, S20 and S18 (in 3 bytes) signed and
+ * unsigned, F32 and F64, each little- and big-endian.  A binding passes GST_AUDIO_INFO_FORMAT through.  Two formats that differ in byte
+ * order only, with no mix and no rate change, are converted by swapping every sample's bytes (the reference's converter_endian):
+ * nothing is unpacked, quantized or dithered, and floats pass with their denormals and NaN payloads. */
 enum {
-  GSTAMD_AFMT_S8 = 2, GSTAMD_AFMT_U8 = 3, GSTAMD_AFMT_S16LE = 4, GSTAMD_AFMT_S24_32LE = 8, GSTAMD_AFMT_S32LE = 12, GSTAMD_AFMT_S24LE = 16,
-  GSTAMD_AFMT_F32LE = 28, GSTAMD_AFMT_F64LE = 30
+  GSTAMD_AFMT_S8 = 2, GSTAMD_AFMT_U8 = 3,
+  GSTAMD_AFMT_S16LE = 4, GSTAMD_AFMT_S16BE = 5, GSTAMD_AFMT_U16LE = 6, GSTAMD_AFMT_U16BE = 7,
+  GSTAMD_AFMT_S24_32LE = 8, GSTAMD_AFMT_S24_32BE = 9, GSTAMD_AFMT_U24_32LE = 10, GSTAMD_AFMT_U24_32BE = 11,
+  GSTAMD_AFMT_S32LE = 12, GSTAMD_AFMT_S32BE = 13, GSTAMD_AFMT_U32LE = 14, GSTAMD_AFMT_U32BE = 15,
+  GSTAMD_AFMT_S24LE = 16, GSTAMD_AFMT_S24BE = 17, GSTAMD_AFMT_U24LE = 18, GSTAMD_AFMT_U24BE = 19,
+  GSTAMD_AFMT_S20LE = 20, GSTAMD_AFMT_S20BE = 21, GSTAMD_AFMT_U20LE = 22, GSTAMD_AFMT_U20BE = 23,
+  GSTAMD_AFMT_S18LE = 24, GSTAMD_AFMT_S18BE = 25, GSTAMD_AFMT_U18LE = 26, GSTAMD_AFMT_U18BE = 27,
+  GSTAMD_AFMT_F32LE = 28, GSTAMD_AFMT_F32BE = 29, GSTAMD_AFMT_F64LE = 30, GSTAMD_AFMT_F64BE = 31
 };
 /* GstAudioDitherMethod / GstAudioNoiseShapingMethod (audio-quantize.h:45-72) */
 enum { GSTAMD_AUDIO_DITHER_NONE = 0, GSTAMD_AUDIO_DITHER_RPDF = 1, GSTAMD_AUDIO_DITHER_TPDF = 2, GSTAMD_AUDIO_DITHER_TPDF_HF = 3 };

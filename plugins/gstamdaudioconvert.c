@@ -21,7 +21,10 @@
 GST_DEBUG_CATEGORY_STATIC (amd_ac_debug);
 #define GST_CAT_DEFAULT amd_ac_debug
 
-#define AMD_AC_CAPS "audio/x-raw, format = (string) { F64LE, F32LE, S32LE, S24_32LE, S24LE, S16LE, S8, U8 }, rate = (int) [ 1, MAX ], " \
+/* every raw format (GST_AUDIO_FORMATS_ALL's set), the little-endian ones first */
+#define AMD_AC_FORMATS "{ F64LE, F32LE, S32LE, S24_32LE, S24LE, S16LE, S8, U8, U32LE, U24_32LE, U24LE, S20LE, U20LE, S18LE, U18LE, U16LE, " \
+    "F64BE, F32BE, S32BE, U32BE, S24_32BE, U24_32BE, S24BE, U24BE, S20BE, U20BE, S18BE, U18BE, S16BE, U16BE }"
+#define AMD_AC_CAPS "audio/x-raw, format = (string) " AMD_AC_FORMATS ", rate = (int) [ 1, MAX ], " \
     "channels = (int) [ 1, 8 ], layout = (string) interleaved"
 
 static GstStaticPadTemplate ac_sink = GST_STATIC_PAD_TEMPLATE ("sink", GST_PAD_SINK, GST_PAD_ALWAYS, GST_STATIC_CAPS (AMD_AC_CAPS));
@@ -263,17 +266,10 @@ amd_ac_info (const GstAudioInfo * i, GstAmdAudioInfo * a)
 {
   gint c;
   memset (a, 0, sizeof (*a));
-  switch (GST_AUDIO_INFO_FORMAT (i)) {
-    case GST_AUDIO_FORMAT_S8: a->format = GSTAMD_AFMT_S8; break;
-    case GST_AUDIO_FORMAT_U8: a->format = GSTAMD_AFMT_U8; break;
-    case GST_AUDIO_FORMAT_S16LE: a->format = GSTAMD_AFMT_S16LE; break;
-    case GST_AUDIO_FORMAT_S24_32LE: a->format = GSTAMD_AFMT_S24_32LE; break;
-    case GST_AUDIO_FORMAT_S32LE: a->format = GSTAMD_AFMT_S32LE; break;
-    case GST_AUDIO_FORMAT_S24LE: a->format = GSTAMD_AFMT_S24LE; break;
-    case GST_AUDIO_FORMAT_F32LE: a->format = GSTAMD_AFMT_F32LE; break;
-    case GST_AUDIO_FORMAT_F64LE: a->format = GSTAMD_AFMT_F64LE; break;
-    default: return FALSE;
-  }
+  /* GSTAMD_AFMT_* are GstAudioFormat's values: every raw format passes through (UNKNOWN and ENCODED are not raw) */
+  if (GST_AUDIO_INFO_FORMAT (i) < GST_AUDIO_FORMAT_S8 || GST_AUDIO_INFO_FORMAT (i) > GST_AUDIO_FORMAT_F64BE)
+    return FALSE;
+  a->format = (int32_t) GST_AUDIO_INFO_FORMAT (i);
   if (GST_AUDIO_INFO_CHANNELS (i) > GSTAMD_AUDIO_MAX_CHANNELS || GST_AUDIO_INFO_LAYOUT (i) != GST_AUDIO_LAYOUT_INTERLEAVED)
     return FALSE;
   a->rate = GST_AUDIO_INFO_RATE (i);
