@@ -175,6 +175,7 @@ for _g, (_n, _bytes) in enumerate((("16", 2), ("24_32", 4), ("32", 4), ("24", 3)
 DITHER = {"none": 0, "rpdf": 1, "tpdf": 2, "tpdf-hf": 3}
 NOISE_SHAPING = {"none": 0, "error-feedback": 1, "simple": 2, "medium": 3, "high": 4}
 MAX_CHANNELS = 8
+LAYOUT = {"interleaved": 0, "non-interleaved": 1}     # GstAudioLayout
 # default positions of gst_audio_info_set_format (audio-info.c: gst_audio_channel_positions ... default_channel_order) for 1 / 2 channels
 DEFAULT_POSITIONS = {1: [-2], 2: [0, 1]}
 # GstAudioChannelPosition (audio-channels.h:101-133)
@@ -215,6 +216,11 @@ def _conv_lib():
         L.gstamd_audio_converter_config_init.argtypes = [C.POINTER(AudioConverterConfig)]
         L.gstamd_audio_converter_new.restype = C.c_void_p
         L.gstamd_audio_converter_new.argtypes = [C.c_int, C.POINTER(AudioInfo), C.POINTER(AudioInfo), C.POINTER(AudioConverterConfig), C.POINTER(C.c_int)]
+        L.gstamd_audio_converter_new_layouts.restype = C.c_void_p
+        L.gstamd_audio_converter_new_layouts.argtypes = [C.c_int, C.POINTER(AudioInfo), C.c_int, C.POINTER(AudioInfo), C.c_int,
+                                                         C.POINTER(AudioConverterConfig), C.POINTER(C.c_int)]
+        L.gstamd_audio_converter_samples_planes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t,
+                                                            C.c_void_p]
         L.gstamd_audio_converter_free.argtypes = [C.c_void_p]
         L.gstamd_audio_converter_reset.argtypes = [C.c_void_p]
         for n in ("get_out_frames", "get_in_frames"):
@@ -249,23 +255,41 @@ def audio_converter_config(dither_method=None, noise_shaping=None, dither_thresh
 
 
 class AudioConverter:
-    """gst_audio_converter_new (flags, in_info, out_info, config) -> .samples (in, in_frames, out, out_frames) on device buffers."""
+    """gst_audio_converter_new (flags, in_info, out_info, config) -> .samples (in, in_frames, out, out_frames) on device buffers.
+    in_layout / out_layout ("interleaved" / "non-interleaved" or 0 / 1) given: gstamd_audio_converter_new_layouts - a non-interleaved side
+    of .samples holds its channels one after the other, .samples_planes takes one buffer per channel."""
 
-    def __init__(self, in_info, out_info, config=None, flags=0):
+    def __init__(self, in_info, out_info, config=None, flags=0, in_layout=None, out_layout=None):
         st = C.c_int(0)
-        self._h = _conv_lib().gstamd_audio_converter_new(flags, C.byref(in_info), C.byref(out_info),
-                                                         C.byref(config) if config is not None else None, C.byref(st))
+        cfg = C.byref(config) if config is not None else None
+        if in_layout is None and out_layout is None:
+            self._h = _conv_lib().gstamd_audio_converter_new(flags, C.byref(in_info), C.byref(out_info), cfg, C.byref(st))
+        else:
+            lay = [LAYOUT[v] if isinstance(v, str) else int(v or 0) for v in (in_layout, out_layout)]
+            self._h = _conv_lib().gstamd_audio_converter_new_layouts(flags, C.byref(in_info), lay[0], C.byref(out_info), lay[1], cfg, C.byref(st))
         if not self._h:
             raise _v.GstAmdError(st.value, _v.last_error())
 
     def get_out_frames(self, in_frames):
         return _conv_lib().gstamd_audio_converter_get_out_frames(self._h, in_frames)
 
+    def get_in_frames(self, out_frames):
+        return _conv_lib().gstamd_audio_converter_get_in_frames(self._h, out_frames)
+
+    def get_max_latency(self):
+        return _conv_lib().gstamd_audio_converter_get_max_latency(self._h)
+
     def is_passthrough(self):
         return bool(_conv_lib().gstamd_audio_converter_is_passthrough(self._h))
 
     def samples(self, src, in_frames, dst, out_frames, stream=None):
         _v._check(_conv_lib().gstamd_audio_converter_samples(self._h, 0, _v._ptr(src), in_frames, _v._ptr(dst), out_frames, stream))
+
+    def samples_planes(self, srcs, in_frames, dsts, out_frames, stream=None):
+        """srcs / dsts: a list with one buffer for an interleaved side, one per channel for a non-interleaved one; srcs None: silence"""
+        ip = (C.c_void_p * len(srcs))(*[_v._ptr(b) for b in srcs]) if srcs is not None else None
+        op = (C.c_void_p * len(dsts))(*[_v._ptr(b) for b in dsts])
+        _v._check(_conv_lib().gstamd_audio_converter_samples_planes(self._h, 0, ip, in_frames, op, out_frames, stream))
 
     def reset(self):
         _conv_lib().gstamd_audio_converter_reset(self._h)

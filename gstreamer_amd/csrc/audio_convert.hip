@@ -63,12 +63,45 @@ __global__ __launch_bounds__ (256) void k_aconv_swap (const uint8_t *in, uint8_t
   aconv_swap_lane<K> (in, out, s, t);
 }
 
+// a non-interleaved side: blockIdx.y is the plane (for a mixing first kernel the output channel), the planes come by
+// value in the kernel arguments.  Consecutive lanes are on consecutive addresses of a plane; the interleaved mid buffer is the strided side.
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_pre_planes (AConvPlan p, AConvPlanes src, uint8_t *__restrict__ mid)
+{
+  aconv_pre_lane_planes<K> (p, src, mid, (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// interleaved frames into a converter whose layout changes (so the mixer runs): blockIdx.y is the output channel, a lane takes four frames
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_pre_mix (AConvPlan p, const uint8_t *__restrict__ in, uint8_t *__restrict__ mid, AConvSplit s)
+{
+  aconv_pre_lane_mix<K> (p, in, mid, s, (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_post_planes (AConvPlan p, const AConvJump *__restrict__ jump, AConvDitherState ds, const uint8_t *__restrict__ mid,
+    AConvPlanes dst, int32_t *__restrict__ qv, int32_t *__restrict__ qd)
+{
+  aconv_post_lane_planes<K> (p, *jump, ds, mid, dst, qv, qd, (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// noise shaping into planes: the reference's quantizer walks plane after plane with one channel's error history, so this is one
+// recurrence over channels x frames samples - one lane
+template <int K>
+__global__ __launch_bounds__ (64) void k_aconv_shape_planes (AConvPlan p, const int32_t *__restrict__ qv, const int32_t *__restrict__ qd, int32_t *__restrict__ hist,
+    AConvPlanes dst)
+{
+  if (threadIdx.x == 0)
+    aconv_shape_planes<K> (p, qv, qd, hist, dst);
+}
+
 static unsigned aconv_blocks (const AConvSplit &s) { return (unsigned) ((aconv_split_lanes (s) + 255) / 256); }
 
 struct GstAmdAudioConverter {
   GstAmdAudioInfo in, out;
   GstAmdAudioConverterConfig cfg;
   int flags = 0;
+  int in_layout = 0, out_layout = 0;                    /* GSTAMD_AUDIO_LAYOUT_* of the two sides */
   AConvPlan plan;
   bool passthrough = false;
   GstAmdAudioResampler *resampler = nullptr;
@@ -99,6 +132,12 @@ void gstamd_audio_converter_config_init (GstAmdAudioConverterConfig *c)
 GstAmdAudioConverter *gstamd_audio_converter_new (int flags, const GstAmdAudioInfo *in, const GstAmdAudioInfo *out, const GstAmdAudioConverterConfig *config,
     int *status)
 {
+  return gstamd_audio_converter_new_layouts (flags, in, GSTAMD_AUDIO_LAYOUT_INTERLEAVED, out, GSTAMD_AUDIO_LAYOUT_INTERLEAVED, config, status);
+}
+
+GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAmdAudioInfo *in, int in_layout, const GstAmdAudioInfo *out, int out_layout,
+    const GstAmdAudioConverterConfig *config, int *status)
+{
   auto fail = [&](int code, const std::string &msg) -> GstAmdAudioConverter * {
     if (status)
       *status = aconv_fail (code, msg);
@@ -118,9 +157,11 @@ GstAmdAudioConverter *gstamd_audio_converter_new (int flags, const GstAmdAudioIn
   c->out = *out;
   c->cfg = cfg;
   c->flags = flags;
+  c->in_layout = in_layout;
+  c->out_layout = out_layout;
   bool resample = false;
   std::string err;
-  const int code = aconv_make_plan (flags, in, out, cfg, &c->plan, &resample, &c->passthrough, &err);
+  const int code = aconv_make_plan_layouts (flags, in, in_layout, out, out_layout, cfg, &c->plan, &resample, &c->passthrough, &err);
   if (code != GSTAMD_OK) {
     delete c;
     return fail (code, err);
@@ -236,49 +277,85 @@ static int ensure (uint8_t **buf, size_t *size, size_t need)
   return GSTAMD_OK;
 }
 
-int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const void *in, size_t in_frames, void *out, size_t out_frames, void *stream_)
+// planes that follow one another without a gap are one run of samples
+static bool planes_contiguous (uint8_t *const *pl, int n, size_t plane_bytes)
 {
-  (void) flags;
-  if (!c || (!out && out_frames))
-    return aconv_fail (GSTAMD_ERR_INVALID, "NULL converter or output");
-  hipStream_t stream = (hipStream_t) stream_;
+  for (int c = 1; c < n; c++)
+    if (pl[c] != pl[c - 1] + plane_bytes)
+      return false;
+  return true;
+}
+
+static void swap_launch (int bytes, const uint8_t *in, uint8_t *out, size_t n, hipStream_t stream)
+{
+  const AConvSplit s = aconv_swap_split (in, out, bytes, n);
+  if (aconv_split_lanes (s) == 0)
+    return;
+  switch (bytes) {
+    case 2: k_aconv_swap<AK_2LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (in, out, s); break;
+    case 3: k_aconv_swap<AK_3LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (in, out, s); break;
+    case 4: k_aconv_swap<AK_4LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (in, out, s); break;
+    default: k_aconv_swap<AK_8LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (in, out, s); break;
+  }
+}
+
+// in[] / out[]: one pointer for an interleaved side, `channels` pointers for a non-interleaved one; in == NULL: silence
+static int aconv_run (GstAmdAudioConverter *c, uint8_t *const *in, size_t in_frames, uint8_t *const *out, size_t out_frames, hipStream_t stream)
+{
   const AConvPlan &p = c->plan;
-  if (in_frames == 0)                           /* gst_audio_converter_samples :1618-1621: "skipping empty buffer" */
-    return GSTAMD_OK;
-  if (c->passthrough) {
+  const size_t in_b = (size_t) afmt_bytes (p.in_fmt), out_b = (size_t) afmt_bytes (p.out_fmt);
+  if (c->passthrough || p.endian_swap) {                /* equal layouts and channel counts: block by block */
     if (!in)
       return aconv_fail (GSTAMD_ERR_INVALID, "NULL input");
-    const size_t bytes = out_frames * (size_t) p.out_ch * (size_t) afmt_bytes (p.out_fmt);
-    if (in != out && hipMemcpyAsync (out, in, bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess)
-      return aconv_fail (GSTAMD_ERR_HIP, "copy");
+    if (!c->passthrough && in_frames != out_frames)
+      return aconv_fail (GSTAMD_ERR_INVALID, "in_frames != out_frames without a resampler");
+    int blocks = c->out_layout ? p.out_ch : 1;
+    size_t n = out_frames * (size_t) (c->out_layout ? 1 : p.out_ch);   /* samples of a block */
+    if (blocks > 1 && planes_contiguous (in, blocks, n * in_b) && planes_contiguous (out, blocks, n * out_b)) {
+      n *= (size_t) blocks;
+      blocks = 1;
+    }
+    for (int b = 0; b < blocks; b++) {
+      if (c->passthrough) {
+        if (in[b] != out[b] && n && hipMemcpyAsync (out[b], in[b], n * out_b, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+          return aconv_fail (GSTAMD_ERR_HIP, "copy");
+      } else {
+        swap_launch (p.endian_swap, in[b], out[b], n, stream);
+      }
+    }
+    if (!c->passthrough && hipGetLastError () != hipSuccess)
+      return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
     return GSTAMD_OK;
   }
   if (!c->resampler && in_frames != out_frames)
     return aconv_fail (GSTAMD_ERR_INVALID, "in_frames != out_frames without a resampler");
-  if (p.endian_swap) {
-    if (!in)
-      return aconv_fail (GSTAMD_ERR_INVALID, "NULL input");
-    const AConvSplit s = aconv_swap_split (in, out, p.endian_swap, out_frames * (size_t) p.out_ch);
-    switch (p.endian_swap) {
-      case 2: k_aconv_swap<AK_2LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
-      case 3: k_aconv_swap<AK_3LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
-      case 4: k_aconv_swap<AK_4LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
-      default: k_aconv_swap<AK_8LE><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> ((const uint8_t *) in, (uint8_t *) out, s); break;
-    }
-    if (hipGetLastError () != hipSuccess)
-      return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
-    return GSTAMD_OK;
-  }
   const size_t mid_bytes_in = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
   int r;
   const uint8_t *after = nullptr;
   if (in) {
     if ((r = ensure (&c->mid_a, &c->mid_a_size, (in_frames ? in_frames : 1) * mid_bytes_in)) != GSTAMD_OK)
       return r;
-    const size_t n = in_frames * (size_t) p.out_ch;
-    if (n) {
-      const AConvSplit s = aconv_split (in, afmt_bytes (p.in_fmt), n, aconv_pre_grouped (p));
-#define PRE(K) k_aconv_pre<K><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (p, (const uint8_t *) in, c->mid_a, s)
+    if (c->in_layout) {
+      AConvPlanes src;
+      memset (&src, 0, sizeof (src));
+      for (int ci = 0; ci < p.in_ch; ci++)
+        src.p[ci] = in[ci];
+      src.frames = in_frames;
+      aconv_planes_heads (&src, p.in_ch, p.out_ch, (int) in_b, aconv_pre_grouped_planes (p), !p.mix);
+      const size_t lanes = aconv_planes_lanes (src, p.out_ch);
+      if (lanes) {
+#define PRE(K) k_aconv_pre_planes<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch), dim3 (256), 0, stream>>> (p, src, c->mid_a)
+        GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+      }
+    } else if (in_frames && c->out_layout && aconv_pre_grouped_mix (p)) {
+      const AConvSplit s = aconv_split (in[0], (int) in_b * p.in_ch, in_frames, true);          /* of the frames */
+#define PRE(K) k_aconv_pre_mix<K><<<dim3 (aconv_blocks (s), (unsigned) p.out_ch), dim3 (256), 0, stream>>> (p, in[0], c->mid_a, s)
+      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+    } else if (in_frames) {
+      const AConvSplit s = aconv_split (in[0], (int) in_b, in_frames * (size_t) p.out_ch, aconv_pre_grouped (p));
+#define PRE(K) k_aconv_pre<K><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (p, in[0], c->mid_a, s)
       GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
 #undef PRE
     }
@@ -289,7 +366,7 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
   if (c->resampler) {
     if ((r = ensure (&c->mid_b, &c->mid_b_size, (out_frames ? out_frames : 1) * mid_bytes_in)) != GSTAMD_OK)
       return r;
-    r = gstamd_audio_resampler_resample (c->resampler, in ? c->mid_a : nullptr, in_frames, c->mid_b, out_frames, stream_);
+    r = gstamd_audio_resampler_resample (c->resampler, in ? c->mid_a : nullptr, in_frames, c->mid_b, out_frames, stream);
     if (r != GSTAMD_OK)
       return r;
     after = c->mid_b;
@@ -297,25 +374,80 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
   const size_t samples = out_frames * (size_t) p.out_ch;
   if (samples == 0)                             /* the resampler only took input into its history */
     return GSTAMD_OK;
-  if (p.ns && p.quant_shift > 0) {
+  const bool shape = p.ns && p.quant_shift > 0;
+  if (shape) {
     if ((r = ensure (&c->q_v, &c->q_v_size, samples * 4)) != GSTAMD_OK || (r = ensure (&c->q_d, &c->q_d_size, samples * 4)) != GSTAMD_OK)
       return r;
   }
-  const AConvSplit s = aconv_split (out, afmt_bytes (p.out_fmt), samples, aconv_post_grouped (p));
-#define POST(K) k_aconv_post<K><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (p, c->jump_dev, c->dither, after, (uint8_t *) out, (int32_t *) c->q_v, \
-    (int32_t *) c->q_d, s)
-  GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+  if (c->out_layout) {
+    AConvPlanes dst;
+    memset (&dst, 0, sizeof (dst));
+    for (int co = 0; co < p.out_ch; co++)
+      dst.p[co] = out[co];
+    dst.frames = out_frames;
+    aconv_planes_heads (&dst, p.out_ch, p.out_ch, (int) out_b, aconv_post_grouped (p), true);
+    const size_t lanes = aconv_planes_lanes (dst, p.out_ch);
+#define POST(K) k_aconv_post_planes<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch), dim3 (256), 0, stream>>> (p, c->jump_dev, c->dither, after, dst, \
+    (int32_t *) c->q_v, (int32_t *) c->q_d)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
 #undef POST
-  if (p.ns && p.quant_shift > 0) {
-#define SHAPE(K) k_aconv_shape<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, (const int32_t *) c->q_v, (const int32_t *) c->q_d, c->hist, (uint8_t *) out, out_frames)
-    GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+    if (shape) {
+#define SHAPE(K) k_aconv_shape_planes<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, (const int32_t *) c->q_v, (const int32_t *) c->q_d, c->hist, dst)
+      GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
 #undef SHAPE
+    }
+  } else {
+    const AConvSplit s = aconv_split (out[0], (int) out_b, samples, aconv_post_grouped (p));
+#define POST(K) k_aconv_post<K><<<dim3 (aconv_blocks (s)), dim3 (256), 0, stream>>> (p, c->jump_dev, c->dither, after, out[0], (int32_t *) c->q_v, \
+    (int32_t *) c->q_d, s)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+    if (shape) {
+#define SHAPE(K) k_aconv_shape<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, (const int32_t *) c->q_v, (const int32_t *) c->q_d, c->hist, out[0], out_frames)
+      GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+    }
   }
   if (hipGetLastError () != hipSuccess)
     return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
   /* the generator moves on by the draws of this call (setup_dither_buf draws for every sample of the block) */
   aconv_dither_advance (p, c->jump_host, &c->dither, samples);
   return GSTAMD_OK;
+}
+
+int gstamd_audio_converter_samples_planes (GstAmdAudioConverter *c, int flags, const void *const in[], size_t in_frames, void *const out[], size_t out_frames,
+    void *stream)
+{
+  (void) flags;
+  if (!c || (!out && out_frames))
+    return aconv_fail (GSTAMD_ERR_INVALID, "NULL converter or output");
+  if (in_frames == 0)                           /* gst_audio_converter_samples :1618-1621: "skipping empty buffer" */
+    return GSTAMD_OK;
+  uint8_t *ip[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr }, *op[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr };
+  for (int k = 0; in && k < (c->in_layout ? c->plan.in_ch : 1); k++)
+    if (!(ip[k] = (uint8_t *) in[k]))
+      return aconv_fail (GSTAMD_ERR_INVALID, "NULL input plane");
+  for (int k = 0; out_frames && k < (c->out_layout ? c->plan.out_ch : 1); k++)
+    if (!(op[k] = (uint8_t *) out[k]))
+      return aconv_fail (GSTAMD_ERR_INVALID, "NULL output plane");
+  return aconv_run (c, in ? ip : nullptr, in_frames, op, out_frames, (hipStream_t) stream);
+}
+
+int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const void *in, size_t in_frames, void *out, size_t out_frames, void *stream)
+{
+  (void) flags;
+  if (!c || (!out && out_frames))
+    return aconv_fail (GSTAMD_ERR_INVALID, "NULL converter or output");
+  if (in_frames == 0)
+    return GSTAMD_OK;
+  /* a non-interleaved side as gstamd_audio_resampler_resample takes it: the channels one after the other, in_frames (out_frames) samples apart */
+  uint8_t *ip[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr }, *op[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr };
+  const size_t in_plane = in_frames * (size_t) afmt_bytes (c->plan.in_fmt), out_plane = out_frames * (size_t) afmt_bytes (c->plan.out_fmt);
+  for (int k = 0; in && k < (c->in_layout ? c->plan.in_ch : 1); k++)
+    ip[k] = (uint8_t *) in + (size_t) k * in_plane;
+  for (int k = 0; k < (c->out_layout ? c->plan.out_ch : 1); k++)
+    op[k] = (uint8_t *) out + (size_t) k * out_plane;
+  return aconv_run (c, in ? ip : nullptr, in_frames, op, out_frames, (hipStream_t) stream);
 }
 
 }  // extern "C"

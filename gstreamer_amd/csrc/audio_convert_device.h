@@ -48,6 +48,19 @@ struct AConvPlan {
   int mi[GSTAMD_AUDIO_MAX_CHANNELS][GSTAMD_AUDIO_MAX_CHANNELS];         // (gint) (m * 1024)
   int sparse;                   // the mixer's sparse form: only the coefficients of use[] are summed
   uint32_t use[GSTAMD_AUDIO_MAX_CHANNELS];                              // [out]: bit ci = input channel ci takes part
+  int q_stride;                 // samples between two frames of a channel as the quantize stage sees them: out_ch, or 1 for a non-interleaved
+                                // output, which gst_audio_quantize_samples walks plane after plane as ONE channel
+};
+
+// the caller-facing side of a non-interleaved converter: the planes by value in the kernel arguments.  head[y]: how row y of the launch
+// (a plane; for the mixing first kernel an output channel) splits its frames - 0 .. 3 single frames up to the dword boundary the
+// four-frame lanes start on (AConvSplit), 4: a lane per frame.  realign: the planes a mixing row reads do not reach a dword boundary at
+// the same frame; the four-frame lanes start at frame 4, end four frames or more before the last, and shift what they load (aconv_load4_any).
+struct AConvPlanes {
+  uint8_t *p[GSTAMD_AUDIO_MAX_CHANNELS];
+  size_t frames;
+  uint8_t head[GSTAMD_AUDIO_MAX_CHANNELS];
+  uint8_t realign;
 };
 
 GSTAMD_AC int amid_bytes (int mid) { return mid == AMID_S16 ? 2 : mid == AMID_F64 ? 8 : 4; }
@@ -191,13 +204,12 @@ template <int N> GSTAMD_AC void aconv_store_words (void *q, const uint32_t *d)
 }
 
 // ---- four consecutive samples on aligned dwords: 4 samples of a B-byte container are B dwords; q is 4-byte aligned ---------------------
-template <int K> GSTAMD_AC void aconv_load4 (const uint8_t *q, uint32_t w[4])
+// d: the B dwords that hold four samples -> the four containers
+template <int K> GSTAMD_AC void aconv_words_to_w4 (const uint32_t *d, uint32_t w[4])
 {
   constexpr int B = akind_bytes (K);
   constexpr bool BE = akind_be (K);
   static_assert (B <= 4, "64-bit containers: aconv_load4_64");
-  uint32_t d[B];
-  aconv_load_words<B> (q, d);
   if constexpr (B == 1) {
     for (int j = 0; j < 4; j++)
       w[j] = (d[0] >> (8 * j)) & 0xffu;
@@ -214,6 +226,31 @@ template <int K> GSTAMD_AC void aconv_load4 (const uint8_t *q, uint32_t w[4])
   } else {
     for (int j = 0; j < 4; j++)
       w[j] = BE ? aconv_bswap32 (d[j]) : d[j];
+  }
+}
+
+template <int K> GSTAMD_AC void aconv_load4 (const uint8_t *q, uint32_t w[4])
+{
+  constexpr int B = akind_bytes (K);
+  uint32_t d[B];
+  aconv_load_words<B> (q, d);
+  aconv_words_to_w4<K> (d, w);
+}
+
+// the same at any address: the B + 1 aligned dwords around the four samples, shifted down by the address' byte phase.  The caller
+// keeps [q - 3, q + 4 B + 4) inside the buffer (aconv_plane_split leaves four frames to single lanes at both ends of a plane for that).
+template <int K> GSTAMD_AC void aconv_load4_any (const uint8_t *q, uint32_t w[4])
+{
+  constexpr int B = akind_bytes (K);
+  if constexpr (B >= 4) {               /* samples of four bytes are aligned */
+    aconv_load4<K> (q, w);
+  } else {
+    const unsigned a = (unsigned) ((uintptr_t) q & 3u);
+    uint32_t x[B + 1], d[B];
+    aconv_load_words<B + 1> (q - a, x);
+    for (int k = 0; k < B; k++)
+      d[k] = (uint32_t) (((((uint64_t) x[k + 1]) << 32) | x[k]) >> (8u * a));
+    aconv_words_to_w4<K> (d, w);
   }
 }
 
@@ -426,7 +463,8 @@ struct AConvDitherState {
   int has_prev;                 // 0: last_random is still the zeros of gst_audio_quantize_setup_dither
 };
 
-// setup_dither_buf (audio-quantize.c:117-170): the dither word of sample index i of the call (interleaved order, draws in that order)
+// setup_dither_buf (audio-quantize.c:117-170): the dither word of sample index i of the call (the order the quantizer walks the call's samples
+// in - interleaved, or plane after plane -, draws in that order)
 GSTAMD_AC int32_t aconv_dither_value (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, size_t i)
 {
   const int shift = p.quant_shift;
@@ -443,7 +481,7 @@ GSTAMD_AC int32_t aconv_dither_value (const AConvPlan &p, const AConvJump &jump,
       return (int32_t) (bias + (uint32_t) r1 + (uint32_t) r2);
     }
     case GSTAMD_AUDIO_DITHER_TPDF_HF: {
-      const size_t stride = (size_t) p.out_ch;
+      const size_t stride = (size_t) p.q_stride;
       uint32_t st = aconv_rand_jump (jump, ds.state0, (uint64_t) i);
       const int32_t tmp = aconv_random_dither (&st, 1 << (shift - 1));
       int32_t last = 0;
@@ -476,7 +514,7 @@ inline void aconv_dither_advance (const AConvPlan &p, const AConvJump &jump, ACo
   if (samples == 0 || aconv_dither_draws (p, samples) == 0)
     return;
   if (p.dither == GSTAMD_AUDIO_DITHER_TPDF_HF) {
-    ds->prev_state = aconv_rand_jump (jump, ds->state0, (uint64_t) (samples - (size_t) p.out_ch));
+    ds->prev_state = aconv_rand_jump (jump, ds->state0, (uint64_t) (samples - (size_t) p.q_stride));
     ds->has_prev = 1;
   }
   ds->state0 = aconv_rand_jump (jump, ds->state0, aconv_dither_draws (p, samples));
@@ -495,7 +533,7 @@ GSTAMD_AC int32_t aconv_quantize (const AConvPlan &p, int32_t d, int32_t v)
 //   gst_audio_quantize_quantize_int_dither_noise_shape   audio-quantize.c:239-278
 template <int K> GSTAMD_AC void aconv_shape_channel (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, uint8_t *out, size_t frames, int c)
 {
-  const size_t ch = (size_t) p.out_ch;
+  const size_t ch = (size_t) p.q_stride;
   const uint32_t mask = ~((1u << p.quant_shift) - 1u);
   if (p.ns == 1) {
     uint32_t e = (uint32_t) hist[c];
@@ -533,23 +571,34 @@ template <int K> GSTAMD_AC void aconv_shape_channel (const AConvPlan &p, const i
     hist[(size_t) j * ch + (size_t) c] = (int32_t) h[j];
 }
 
-// ---- stage 1: input frame n, output channel co -> one sample in the mid_in format ------------------------------------------------
-template <int K> GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t *mid, size_t n, int co)
+// ---- where sample (frame n, channel ci) of the caller's input is: interleaved frames, or one plane per channel -------------------------
+struct AConvSrcFrames {
+  const uint8_t *in;
+  GSTAMD_AC const uint8_t *at (const AConvPlan &p, int bytes, size_t n, int ci) const { return in + (size_t) bytes * (n * (size_t) p.in_ch + (size_t) ci); }
+};
+
+struct AConvSrcPlanes {
+  const AConvPlanes &pl;
+  GSTAMD_AC const uint8_t *at (const AConvPlan &, int bytes, size_t n, int ci) const { return pl.p[ci] + (size_t) bytes * n; }
+};
+
+// ---- stage 1: input frame n, output channel co -> one sample in the mid_in format (the mid buffers are interleaved frames) --------------
+template <int K, class Src> GSTAMD_AC void aconv_pre_sample_at (const AConvPlan &p, const Src &src, uint8_t *mid, size_t n, int co)
 {
+  constexpr int B = akind_bytes (K);
   const size_t o = n * (size_t) p.out_ch + (size_t) co;
-  const size_t ibase = n * (size_t) p.in_ch;
   switch (p.mid_in) {
     case AMID_S16: {            // same 16-bit format in and out: the samples themselves
       int32_t res;
       if (!p.mix) {
-        int16_t v; memcpy (&v, in + 2 * (ibase + co), 2);
+        int16_t v; memcpy (&v, src.at (p, 2, n, co), 2);
         res = v;
       } else {
         res = 0;
         for (int ci = 0; ci < p.in_ch; ci++) {
           if (!((p.use[co] >> ci) & 1u))
             continue;
-          int16_t v; memcpy (&v, in + 2 * (ibase + ci), 2);
+          int16_t v; memcpy (&v, src.at (p, 2, n, ci), 2);
           res += (int32_t) v * p.mi[ci][co];
         }
         res = (res + 512) >> 10;
@@ -562,12 +611,12 @@ template <int K> GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint
     case AMID_S32: {
       int32_t r;
       if (!p.mix) {
-        r = aconv_unpack_int<K> (p, in, ibase + co);
+        r = aconv_unpack_int<K> (p, src.at (p, B, n, co), 0);
       } else {
         int64_t res = 0;
         for (int ci = 0; ci < p.in_ch; ci++)
           if ((p.use[co] >> ci) & 1u)
-            res += (int64_t) aconv_unpack_int<K> (p, in, ibase + ci) * (int64_t) p.mi[ci][co];
+            res += (int64_t) aconv_unpack_int<K> (p, src.at (p, B, n, ci), 0) * (int64_t) p.mi[ci][co];
         res = (res + 512) >> 10;
         r = res > 2147483647ll ? 2147483647 : (res < -2147483648ll ? (int32_t) 0x80000000u : (int32_t) res);
       }
@@ -577,13 +626,13 @@ template <int K> GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint
     case AMID_F32: {            // F32 in and out: the mixer works in single precision
       float r;
       if (!p.mix) {
-        memcpy (&r, in + 4 * (ibase + co), 4);
+        memcpy (&r, src.at (p, 4, n, co), 4);
       } else {
         r = 0.0f;
         for (int ci = 0; ci < p.in_ch; ci++) {
           if (!((p.use[co] >> ci) & 1u))
             continue;
-          float v; memcpy (&v, in + 4 * (ibase + ci), 4);
+          float v; memcpy (&v, src.at (p, 4, n, ci), 4);
           r += v * p.m[ci][co];
         }
       }
@@ -593,19 +642,60 @@ template <int K> GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint
     default: {
       double r;
       if (!p.mix) {
-        r = p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, in, ibase + co)) : aconv_unpack_flt<K> (in, ibase + co);
+        r = p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, src.at (p, B, n, co), 0)) : aconv_unpack_flt<K> (src.at (p, B, n, co), 0);
       } else {
         r = 0.0;
         for (int ci = 0; ci < p.in_ch; ci++) {
           if (!((p.use[co] >> ci) & 1u))
             continue;
-          const double v = p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, in, ibase + ci)) : aconv_unpack_flt<K> (in, ibase + ci);
+          const double v = p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, src.at (p, B, n, ci), 0)) : aconv_unpack_flt<K> (src.at (p, B, n, ci), 0);
           r += v * p.m[ci][co];
         }
       }
       memcpy (mid + 8 * o, &r, 8);
       break;
     }
+  }
+}
+
+template <int K> GSTAMD_AC void aconv_pre_sample (const AConvPlan &p, const uint8_t *in, uint8_t *mid, size_t n, int co)
+{
+  aconv_pre_sample_at<K> (p, AConvSrcFrames { in }, mid, n, co);
+}
+
+// four consecutive samples of the caller's buffer (q on a dword; ANY: wherever they are, aconv_load4_any) in the mid_in format: S32 ...
+template <int K, bool ANY = false> GSTAMD_AC void aconv_unpack4_s32 (const AConvPlan &p, const uint8_t *q, int32_t r[4])
+{
+  if constexpr (akind_bytes (K) <= 4) {
+    uint32_t w[4];
+    if constexpr (ANY)
+      aconv_load4_any<K> (q, w);
+    else
+      aconv_load4<K> (q, w);
+    for (int j = 0; j < 4; j++)
+      r[j] = aconv_w_to_s32 (p, w[j]);
+  } else {                              /* the 64-bit containers are float formats: the plan never puts S32 behind them */
+    for (int j = 0; j < 4; j++)
+      r[j] = 0;
+  }
+}
+
+// ... or F64 (convert_in after an integer unpack, or the float unpack)
+template <int K, bool ANY = false> GSTAMD_AC void aconv_unpack4_f64 (const AConvPlan &p, const uint8_t *q, double r[4])
+{
+  if constexpr (akind_bytes (K) <= 4) {
+    uint32_t w[4];
+    if constexpr (ANY)
+      aconv_load4_any<K> (q, w);
+    else
+      aconv_load4<K> (q, w);
+    for (int j = 0; j < 4; j++)
+      r[j] = p.convert_in ? aconv_s32_to_double (aconv_w_to_s32 (p, w[j])) : aconv_f32w_to_double (w[j]);
+  } else {
+    uint64_t w[4];
+    aconv_load4_64<K> (q, w);
+    for (int j = 0; j < 4; j++)
+      r[j] = bits_d (w[j]);
   }
 }
 
@@ -622,31 +712,85 @@ template <int K> GSTAMD_AC void aconv_pre_lane (const AConvPlan &p, const uint8_
   const size_t i = s.head + 4 * t;
   const uint8_t *q = in + (size_t) B * i;
   if (p.mid_in == AMID_S32) {
-    if constexpr (B <= 4) {
-      uint32_t w[4];
-      uint32_t r[4];
-      aconv_load4<K> (q, w);
-      for (int j = 0; j < 4; j++)
-        r[j] = (uint32_t) aconv_w_to_s32 (p, w[j]);
-      aconv_store_words<4> (mid + 4 * i, r);
-    }
+    int32_t r[4];
+    uint32_t rw[4];
+    aconv_unpack4_s32<K> (p, q, r);
+    for (int j = 0; j < 4; j++)
+      rw[j] = (uint32_t) r[j];
+    aconv_store_words<4> (mid + 4 * i, rw);
     return;
   }
   double r[4];
-  if constexpr (B <= 4) {
-    uint32_t w[4];
-    aconv_load4<K> (q, w);
-    for (int j = 0; j < 4; j++)
-      r[j] = p.convert_in ? aconv_s32_to_double (aconv_w_to_s32 (p, w[j])) : aconv_f32w_to_double (w[j]);
-  } else {
-    uint64_t w[4];
-    aconv_load4_64<K> (q, w);
-    for (int j = 0; j < 4; j++)
-      r[j] = bits_d (w[j]);
-  }
+  aconv_unpack4_f64<K> (p, q, r);
   uint32_t rw[8];
   memcpy (rw, r, 32);
   aconv_store_words<8> (mid + 8 * i, rw);
+}
+
+// the mixer's saturating ends (gst_audio_channel_mixer_mix_int32)
+GSTAMD_AC int32_t aconv_mix_round_s32 (int64_t res)
+{
+  res = (res + 512) >> 10;
+  return res > 2147483647ll ? 2147483647 : (res < -2147483648ll ? (int32_t) 0x80000000u : (int32_t) res);
+}
+
+// the mixing first kernel on interleaved frames: lane t of output channel co takes four whole frames - in_ch runs of four samples, B
+// aligned dwords each - and adds every sample to the sum of its frame; a frame's samples come by in ascending channel order, so the sums
+// are those of aconv_pre_sample_at.  s: the split of the FRAMES (aconv_split with in_ch * B bytes a frame).
+template <int K> GSTAMD_AC void aconv_pre_lane_mix (const AConvPlan &p, const uint8_t *in, uint8_t *mid, const AConvSplit &s, int co, size_t t)
+{
+  if (t >= aconv_split_lanes (s))
+    return;
+  if (t >= s.groups) {
+    aconv_pre_sample<K> (p, in, mid, aconv_split_single (s, t), co);
+    return;
+  }
+  constexpr int B = akind_bytes (K);
+  const size_t n = s.head + 4 * t, och = (size_t) p.out_ch;
+  const uint8_t *q = in + (size_t) B * n * (size_t) p.in_ch;
+  const uint32_t use = p.use[co];
+  int f = 0, ci = 0;                    /* frame (of the lane's four) and channel of the next sample */
+  if (p.mid_in == AMID_S32) {
+    int64_t res[4] = { 0, 0, 0, 0 };
+    for (int g = 0; g < p.in_ch; g++) {
+      int32_t r[4];
+      aconv_unpack4_s32<K> (p, q + (size_t) (4 * B) * (size_t) g, r);
+      for (int jj = 0; jj < 4; jj++) {
+        if ((use >> ci) & 1u) {
+          const int64_t x = (int64_t) r[jj] * (int64_t) p.mi[ci][co];
+          for (int j = 0; j < 4; j++)
+            res[j] = f == j ? res[j] + x : res[j];
+        }
+        if (++ci == p.in_ch) {
+          ci = 0;
+          f++;
+        }
+      }
+    }
+    for (int j = 0; j < 4; j++) {
+      const int32_t r = aconv_mix_round_s32 (res[j]);
+      memcpy (mid + 4 * ((n + (size_t) j) * och + (size_t) co), &r, 4);
+    }
+    return;
+  }
+  double acc[4] = { 0.0, 0.0, 0.0, 0.0 };
+  for (int g = 0; g < p.in_ch; g++) {
+    double r[4];
+    aconv_unpack4_f64<K> (p, q + (size_t) (4 * B) * (size_t) g, r);
+    for (int jj = 0; jj < 4; jj++) {
+      if ((use >> ci) & 1u) {
+        const double x = r[jj] * p.m[ci][co];
+        for (int j = 0; j < 4; j++)
+          acc[j] = f == j ? acc[j] + x : acc[j];
+      }
+      if (++ci == p.in_ch) {
+        ci = 0;
+        f++;
+      }
+    }
+  }
+  for (int j = 0; j < 4; j++)
+    memcpy (mid + 8 * ((n + (size_t) j) * och + (size_t) co), &acc[j], 8);
 }
 
 // the first kernel's lanes can take four samples each: no mix (so no gather over the input channels), S32 or F64 behind it
@@ -655,8 +799,9 @@ GSTAMD_AC bool aconv_post_grouped (const AConvPlan &p) { return p.mid_in == AMID
 
 // ---- stage 2: sample i (interleaved index) of the mid buffer after the resampler -> the output format -----------------------------
 // convert_out and the quantize stage without noise shaping: the S32 sample that is packed.  With noise shaping (returns true) the
-// sample and its dither word are for aconv_shape_channel instead.
-GSTAMD_AC bool aconv_post_int (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, size_t i, int32_t *v, int32_t *d)
+// sample and its dither word are for aconv_shape_channel instead.  i: the sample's place in the mid buffer; qi: its place in the order
+// the quantizer walks the call in (the same for an interleaved output; plane * frames + frame for a non-interleaved one).
+GSTAMD_AC bool aconv_post_int (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, size_t i, size_t qi, int32_t *v, int32_t *d)
 {
   if (p.convert_out) {
     double x; memcpy (&x, mid + 8 * i, 8);
@@ -665,7 +810,7 @@ GSTAMD_AC bool aconv_post_int (const AConvPlan &p, const AConvJump &jump, const 
     memcpy (v, mid + 4 * i, 4);
   }
   if (p.quant_shift > 0) {
-    *d = aconv_dither_value (p, jump, ds, i);
+    *d = aconv_dither_value (p, jump, ds, qi);
     if (p.ns)
       return true;
     *v = aconv_quantize (p, *d, *v);
@@ -673,29 +818,36 @@ GSTAMD_AC bool aconv_post_int (const AConvPlan &p, const AConvJump &jump, const 
   return false;
 }
 
-template <int K> GSTAMD_AC void aconv_post_sample (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, int32_t *qv,
-    int32_t *qd, size_t i)
+// dst: where the packed sample goes
+template <int K> GSTAMD_AC void aconv_post_sample_at (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, size_t i, uint8_t *dst,
+    int32_t *qv, int32_t *qd, size_t qi)
 {
   if (p.mid_in == AMID_S16) {
-    memcpy (out + 2 * i, mid + 2 * i, 2);
+    memcpy (dst, mid + 2 * i, 2);
     return;
   }
   if (p.mid_in == AMID_F32) {
-    memcpy (out + 4 * i, mid + 4 * i, 4);
+    memcpy (dst, mid + 4 * i, 4);
     return;
   }
   if (p.mid_out == AMID_F64) {
     double v; memcpy (&v, mid + 8 * i, 8);
-    aconv_pack_flt<K> (out, i, v);
+    aconv_pack_flt<K> (dst, 0, v);
     return;
   }
   int32_t v, d = 0;
-  if (aconv_post_int (p, jump, ds, mid, i, &v, &d)) {
-    qv[i] = v;
-    qd[i] = d;
+  if (aconv_post_int (p, jump, ds, mid, i, qi, &v, &d)) {
+    qv[qi] = v;
+    qd[qi] = d;
     return;
   }
-  aconv_pack_int<K> (p, out, i, v);
+  aconv_pack_int<K> (p, dst, 0, v);
+}
+
+template <int K> GSTAMD_AC void aconv_post_sample (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, int32_t *qv,
+    int32_t *qd, size_t i)
+{
+  aconv_post_sample_at<K> (p, jump, ds, mid, i, out + (size_t) akind_bytes (K) * i, qv, qd, i);
 }
 
 // a lane of the second kernel; a lane of the grouped part writes four samples as B dwords of the caller's buffer
@@ -731,7 +883,7 @@ template <int K> GSTAMD_AC void aconv_post_lane (const AConvPlan &p, const AConv
     int32_t v[4], d[4] = { 0, 0, 0, 0 };
     bool shaped = false;
     for (int j = 0; j < 4; j++)
-      shaped = aconv_post_int (p, jump, ds, mid, i + (size_t) j, &v[j], &d[j]);       /* (uniform over the launch) */
+      shaped = aconv_post_int (p, jump, ds, mid, i + (size_t) j, i + (size_t) j, &v[j], &d[j]);       /* (uniform over the launch) */
     if (shaped) {
       for (int j = 0; j < 4; j++) {
         qv[i + (size_t) j] = v[j];
@@ -745,6 +897,167 @@ template <int K> GSTAMD_AC void aconv_post_lane (const AConvPlan &p, const AConv
     aconv_store4<K> (q, w);
   }
 }
+
+// ---- a non-interleaved side: row y of a launch is a plane, its lanes take four consecutive frames of it on aligned dwords (the unpack /
+// pack bodies above as they are) or one frame; what is strided is the interleaved mid buffer ---------------------------------------
+GSTAMD_AC AConvSplit aconv_plane_split (const AConvPlanes &pl, int y)
+{
+  AConvSplit s = { 0, 0, pl.frames };
+  if (pl.realign) {                     /* (frames >= 12: aconv_planes_heads) */
+    s.head = 4;
+    s.groups = (pl.frames - 8) / 4;
+  } else if (pl.head[y] < 4 && pl.frames >= (size_t) pl.head[y] + 4) {
+    s.head = pl.head[y];
+    s.groups = (pl.frames - s.head) / 4;
+  }
+  return s;
+}
+
+// the first kernel: lane t of output channel co.  The mixer's sums run over the input planes in ascending order as in aconv_pre_sample_at;
+// a four-frame lane reads B dwords of every plane it uses - aligned ones where all planes reach a dword boundary at the same frame
+// (aconv_planes_heads), B + 1 around its frames otherwise (ANY)
+template <int K, bool ANY> GSTAMD_AC void aconv_pre_group_planes (const AConvPlan &p, const AConvPlanes &src, uint8_t *mid, int co, size_t n)
+{
+  constexpr int B = akind_bytes (K);
+  const size_t och = (size_t) p.out_ch;
+  const uint32_t use = p.mix ? p.use[co] : 1u << co;
+  if (p.mid_in == AMID_S32) {
+    int64_t res[4] = { 0, 0, 0, 0 };
+    int32_t r[4] = { 0, 0, 0, 0 };
+    for (int ci = 0; ci < p.in_ch; ci++) {
+      if (!((use >> ci) & 1u))
+        continue;
+      aconv_unpack4_s32<K, ANY> (p, src.p[ci] + (size_t) B * n, r);
+      for (int j = 0; j < 4; j++)
+        res[j] += (int64_t) r[j] * (int64_t) p.mi[ci][co];
+    }
+    for (int j = 0; j < 4; j++) {
+      const int32_t x = p.mix ? aconv_mix_round_s32 (res[j]) : r[j];
+      memcpy (mid + 4 * ((n + (size_t) j) * och + (size_t) co), &x, 4);
+    }
+    return;
+  }
+  double acc[4] = { 0.0, 0.0, 0.0, 0.0 }, r[4] = { 0.0, 0.0, 0.0, 0.0 };
+  for (int ci = 0; ci < p.in_ch; ci++) {
+    if (!((use >> ci) & 1u))
+      continue;
+    aconv_unpack4_f64<K, ANY> (p, src.p[ci] + (size_t) B * n, r);
+    for (int j = 0; j < 4; j++)
+      acc[j] += r[j] * p.m[ci][co];
+  }
+  for (int j = 0; j < 4; j++) {
+    const double x = p.mix ? acc[j] : r[j];
+    memcpy (mid + 8 * ((n + (size_t) j) * och + (size_t) co), &x, 8);
+  }
+}
+
+template <int K> GSTAMD_AC void aconv_pre_lane_planes (const AConvPlan &p, const AConvPlanes &src, uint8_t *mid, int co, size_t t)
+{
+  const AConvSplit s = aconv_plane_split (src, co);
+  if (t >= aconv_split_lanes (s))
+    return;
+  if (t >= s.groups) {
+    aconv_pre_sample_at<K> (p, AConvSrcPlanes { src }, mid, aconv_split_single (s, t), co);
+    return;
+  }
+  if (src.realign)
+    aconv_pre_group_planes<K, true> (p, src, mid, co, s.head + 4 * t);
+  else
+    aconv_pre_group_planes<K, false> (p, src, mid, co, s.head + 4 * t);
+}
+
+// the second kernel: lane t of output plane c
+template <int K> GSTAMD_AC void aconv_post_lane_planes (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, const AConvPlanes &dst,
+    int32_t *qv, int32_t *qd, int c, size_t t)
+{
+  const AConvSplit s = aconv_plane_split (dst, c);
+  if (t >= aconv_split_lanes (s))
+    return;
+  constexpr int B = akind_bytes (K);
+  const size_t och = (size_t) p.out_ch, q0 = (size_t) c * dst.frames;
+  if (t >= s.groups) {
+    const size_t n = aconv_split_single (s, t);
+    aconv_post_sample_at<K> (p, jump, ds, mid, n * och + (size_t) c, dst.p[c] + (size_t) B * n, qv, qd, q0 + n);
+    return;
+  }
+  const size_t n = s.head + 4 * t;
+  uint8_t *q = dst.p[c] + (size_t) B * n;
+  if (p.mid_out == AMID_F64) {
+    double v[4];
+    for (int j = 0; j < 4; j++)
+      memcpy (&v[j], mid + 8 * ((n + (size_t) j) * och + (size_t) c), 8);
+    if constexpr (B == 4) {
+      uint32_t w[4];
+      for (int j = 0; j < 4; j++)
+        w[j] = aconv_double_to_f32w (v[j]);
+      aconv_store4<K> (q, w);
+    } else if constexpr (B == 8) {
+      uint64_t w[4];
+      for (int j = 0; j < 4; j++)
+        w[j] = d_bits (v[j]);
+      aconv_store4_64<K> (q, w);
+    }
+    return;
+  }
+  if constexpr (B <= 4) {
+    int32_t v[4], d[4] = { 0, 0, 0, 0 };
+    bool shaped = false;
+    for (int j = 0; j < 4; j++)
+      shaped = aconv_post_int (p, jump, ds, mid, (n + (size_t) j) * och + (size_t) c, q0 + n + (size_t) j, &v[j], &d[j]);
+    if (shaped) {
+      for (int j = 0; j < 4; j++) {
+        qv[q0 + n + (size_t) j] = v[j];
+        qd[q0 + n + (size_t) j] = d[j];
+      }
+      return;
+    }
+    uint32_t w[4];
+    for (int j = 0; j < 4; j++)
+      w[j] = aconv_s32_to_w (p, v[j]);
+    aconv_store4<K> (q, w);
+  }
+}
+
+// noise shaping into a non-interleaved output: ONE recurrence over plane 0, plane 1, ... of the call (the plan's q_stride is 1, the
+// history one channel's, carried from each plane into the next)
+template <int K> GSTAMD_AC void aconv_shape_planes (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, const AConvPlanes &dst)
+{
+  for (int c = 0; c < p.out_ch; c++)
+    aconv_shape_channel<K> (p, v + (size_t) c * dst.frames, d + (size_t) c * dst.frames, hist, dst.p[c], dst.frames, 0);
+}
+
+// head[] of a launch's rows (host).  rows_are_planes: row y works on plane y alone (the second kernel; the first one without a mix);
+// otherwise every row reads all the planes: where they reach a dword boundary at the same frame the four-frame lanes start there, where they
+// do not (1- to 3-byte samples in planes of different phase) the lanes realign what they load.
+inline void aconv_planes_heads (AConvPlanes *pl, int planes, int rows, int bytes, bool grouped, bool rows_are_planes)
+{
+  uint8_t h[GSTAMD_AUDIO_MAX_CHANNELS];
+  bool same = true;
+  for (int c = 0; c < planes; c++) {
+    const AConvSplit s = aconv_split (pl->p[c], bytes, pl->frames, grouped);
+    h[c] = s.groups ? (uint8_t) s.head : 4;
+    same = same && h[c] == h[0];
+  }
+  for (int y = 0; y < GSTAMD_AUDIO_MAX_CHANNELS; y++)
+    pl->head[y] = y >= rows ? 4 : rows_are_planes ? h[y] : (same ? h[0] : 4);
+  pl->realign = grouped && !rows_are_planes && !same && bytes < 4 && pl->frames >= 12 ? 1 : 0;
+}
+
+// lanes of the longest row
+inline size_t aconv_planes_lanes (const AConvPlanes &pl, int rows)
+{
+  size_t m = 0;
+  for (int y = 0; y < rows; y++) {
+    const size_t l = aconv_split_lanes (aconv_plane_split (pl, y));
+    m = l > m ? l : m;
+  }
+  return m;
+}
+
+// four-frame lanes on a non-interleaved input also serve the mixer (which a layout change always runs)
+GSTAMD_AC bool aconv_pre_grouped_planes (const AConvPlan &p) { return p.mid_in == AMID_S32 || p.mid_in == AMID_F64; }
+// ... and on interleaved frames whose layout changes (aconv_pre_lane_mix; the mixer between two interleaved sides keeps its lane per sample)
+GSTAMD_AC bool aconv_pre_grouped_mix (const AConvPlan &p) { return p.mix && (p.mid_in == AMID_S32 || p.mid_in == AMID_F64); }
 
 // ---- the endian plan (converter_endian): every sample's bytes reversed, nothing else.  K is the little-endian container of the width;
 // reading it as LE and writing it as BE is the swap in either direction.  in == out is fine: a lane reads its bytes before it writes them.

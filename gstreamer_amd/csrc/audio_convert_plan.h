@@ -249,9 +249,17 @@ static void default_mix_matrix (const GstAmdAudioInfo &in, const GstAmdAudioInfo
 
 // The whole plan.  *resample: a resampler (on p->mid_in, out->channels) sits between the two kernels; *passthrough: the bytes
 // themselves; plan->endian_swap: the bytes of every sample reversed.  Returns GSTAMD_OK or an error code with *err set.
-inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAudioInfo *out, const GstAmdAudioConverterConfig &cfg, AConvPlan *plan,
-    bool *resample, bool *passthrough, std::string *err)
+// The layouts (GstAudioLayout: 0 interleaved, 1 non-interleaved) come beside the infos, whose own `layout` stays 0:
+//   - the passthrough and the endian shortcut need equal layouts; where the layouts differ the mix stage runs even with a passthrough
+//     matrix (the mixer is what changes the layout), on the intermediate format the rules below give anyway;
+//   - the quantizer of a non-interleaved output walks plane after plane as one channel: q_stride 1.
+inline int aconv_make_plan_layouts (int flags, const GstAmdAudioInfo *in, int in_layout, const GstAmdAudioInfo *out, int out_layout,
+    const GstAmdAudioConverterConfig &cfg, AConvPlan *plan, bool *resample, bool *passthrough, std::string *err)
 {
+  if (in_layout < 0 || in_layout > 1 || out_layout < 0 || out_layout > 1) {
+    *err = "layout is 0 (interleaved) or 1 (non-interleaved)";
+    return GSTAMD_ERR_INVALID;
+  }
   const AFmtInfo fi = afmt_info (in->format), fo = afmt_info (out->format);
   if (!fi.known || !fo.known) {
     *err = "not a raw sample format (GstAudioFormat 2 .. 31: S8 / U8, S16 / S24_32 / S32 / S24 / S20 / S18 signed and unsigned, F32 / F64, either byte order)";
@@ -262,7 +270,7 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
     return GSTAMD_ERR_UNSUPPORTED;
   }
   if (in->layout != 0 || out->layout != 0) {
-    *err = "non-interleaved layouts are not built into the converter yet";
+    *err = "GstAmdAudioInfo.layout is 0: non-interleaved layouts are the layout arguments of gstamd_audio_converter_new_layouts";
     return GSTAMD_ERR_UNSUPPORTED;
   }
   if (in->rate <= 0 || out->rate <= 0) {
@@ -280,6 +288,7 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
   p.out_fmt = out->format;
   p.in_ch = in->channels;
   p.out_ch = out->channels;
+  p.q_stride = out_layout ? 1 : out->channels;
   {
     const AFmtDesc di = afmt_desc (in->format), dout = afmt_desc (out->format);
     p.in_kind = afmt_kind (in->format);
@@ -327,7 +336,7 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
       const float tmp = p.m[ci][co] * (float) (1 << 10);        /* gst_audio_channel_mixer_setup_matrix_int */
       p.mi[ci][co] = (int) tmp;
     }
-  bool mix_passthrough = in->channels == out->channels;
+  bool mix_passthrough = in->channels == out->channels && in_layout == out_layout;
   for (int i = 0; i < in->channels && mix_passthrough; i++)
     for (int j = 0; j < out->channels && mix_passthrough; j++)
       mix_passthrough = p.m[i][j] == (i == j ? 1.0f : 0.0f);
@@ -378,6 +387,13 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
     p.quant_shift = p.dither = p.ns = p.n_coeffs = 0;           /* this chain has no quantizer */
   }
   return GSTAMD_OK;
+}
+
+// gst_audio_converter_new with two interleaved infos
+inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAudioInfo *out, const GstAmdAudioConverterConfig &cfg, AConvPlan *plan,
+    bool *resample, bool *passthrough, std::string *err)
+{
+  return aconv_make_plan_layouts (flags, in, 0, out, 0, cfg, plan, resample, passthrough, err);
 }
 
 }  // namespace gstamd

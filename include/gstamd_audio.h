@@ -136,11 +136,12 @@ enum {
 /* GstAudioDitherMethod / GstAudioNoiseShapingMethod (audio-quantize.h:45-72) */
 enum { GSTAMD_AUDIO_DITHER_NONE = 0, GSTAMD_AUDIO_DITHER_RPDF = 1, GSTAMD_AUDIO_DITHER_TPDF = 2, GSTAMD_AUDIO_DITHER_TPDF_HF = 3 };
 #define GSTAMD_AUDIO_MAX_CHANNELS 8
+enum { GSTAMD_AUDIO_LAYOUT_INTERLEAVED = 0, GSTAMD_AUDIO_LAYOUT_NON_INTERLEAVED = 1 };  /* GstAudioLayout */
 
 typedef struct GstAmdAudioInfo {
   int32_t format;               /* GSTAMD_AFMT_* */
   int32_t rate, channels;
-  int32_t layout;               /* 0 interleaved (the only layout of the converter so far) */
+  int32_t layout;               /* 0: the converter's layouts are arguments of gstamd_audio_converter_new_layouts, not this field */
   int32_t unpositioned;         /* GST_AUDIO_FLAG_UNPOSITIONED */
   int32_t position[GSTAMD_AUDIO_MAX_CHANNELS];  /* GstAudioChannelPosition values (audio-channels.h:101-133): NONE -3, MONO -2, FRONT_LEFT 0, FRONT_RIGHT 1, FRONT_CENTER 2, LFE1 3, REAR_LEFT 4, ... */
 } GstAmdAudioInfo;
@@ -163,6 +164,13 @@ void gstamd_audio_converter_config_init (GstAmdAudioConverterConfig *config);
  * (GSTAMD_ERR_UNSUPPORTED: the reference converts this, the GPU path does not yet - never a CPU fallback). */
 GstAmdAudioConverter *gstamd_audio_converter_new (int flags, const GstAmdAudioInfo *in_info, const GstAmdAudioInfo *out_info,
     const GstAmdAudioConverterConfig *config, int *status);
+/* gst_audio_converter_new with the layouts of the two GstAudioInfos given beside them.  in_info->layout and out_info->layout must be 0
+ * here as in gstamd_audio_converter_new (which keeps refusing a non-zero one): the layouts are these two arguments; (.., 0, .., 0, ..)
+ * makes the converter gstamd_audio_converter_new makes.  What a non-interleaved side changes: the passthrough and the
+ * byte-swap shortcut need equal layouts; where the layouts differ the mix stage runs even with an identity matrix; the quantizer of a
+ * non-interleaved output dithers and shapes plane after plane as ONE channel, as gst_audio_quantize_samples does. */
+GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAmdAudioInfo *in_info, int in_layout,
+    const GstAmdAudioInfo *out_info, int out_layout, const GstAmdAudioConverterConfig *config, int *status);
 void gstamd_audio_converter_free (GstAmdAudioConverter *convert);
 void gstamd_audio_converter_reset (GstAmdAudioConverter *convert);
 size_t gstamd_audio_converter_get_out_frames (GstAmdAudioConverter *convert, size_t in_frames);
@@ -170,9 +178,15 @@ size_t gstamd_audio_converter_get_in_frames (GstAmdAudioConverter *convert, size
 size_t gstamd_audio_converter_get_max_latency (GstAmdAudioConverter *convert);
 int gstamd_audio_converter_is_passthrough (GstAmdAudioConverter *convert);
 /* gst_audio_converter_samples (audio-converter.c:1545): in / out are device pointers to interleaved frames; in == NULL feeds
- * silence into the resampler (drain) */
+ * silence into the resampler (drain).  A non-interleaved side (gstamd_audio_converter_new_layouts) holds its channels one after the
+ * other, in_frames (out_frames) samples apart, as in gstamd_audio_resampler_resample. */
 int gstamd_audio_converter_samples (GstAmdAudioConverter *convert, int flags, const void *in, size_t in_frames, void *out, size_t out_frames,
     void *stream);
+/* gst_audio_converter_samples' own argument shape: in[] / out[] hold ONE pointer for an interleaved side and `channels` pointers for a
+ * non-interleaved one (any device addresses aligned to the sample size; planes need not be equally spaced); in == NULL feeds silence
+ * into the resampler */
+int gstamd_audio_converter_samples_planes (GstAmdAudioConverter *convert, int flags, const void *const in[], size_t in_frames,
+    void *const out[], size_t out_frames, void *stream);
 /* the mix matrix the converter uses, matrix[in][out] as GstAudioChannelMixer holds it; returns in_channels * out_channels */
 int gstamd_audio_converter_get_mix_matrix (GstAmdAudioConverter *convert, float *matrix, int max);
 

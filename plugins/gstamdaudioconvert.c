@@ -5,8 +5,11 @@
  * dithering-threshold (:350-391), the caps transformation that frees format, layout and - for positioned layouts or with a
  * mix-matrix - channels (:1094-1196), passthrough-first fixation (:1498-1546), a converter made per caps with the element's
  * properties as its config (:1548-1636), silence for GAP buffers (:1733-1747), the GstRequestAudioMixMatrix upstream event
- * (:309-337).  Samples are staged to HBM per buffer like the audioresample element's.
- * Not implemented: input-channels-reorder / -mode, non-interleaved layouts, the depth / sign scoring of fixate_format (:1237-1340;
+ * (:309-337).  Samples are staged to HBM per buffer like the audioresample element's.  Both layouts on both pads: a non-interleaved
+ * side is staged as [channels][frames] (the planes of an input buffer are where its GstAudioMeta says, those of an output buffer back
+ * to back with a GstAudioMeta added, as in gstamdaudioresample.c) and converted by gstamd_audio_converter_new_layouts; fixation
+ * prefers the input's layout.
+ * Not implemented: input-channels-reorder / -mode, the depth / sign scoring of fixate_format (:1237-1340;
  * this element prefers the input's format, then the widest one the peer offers of the same kind).
  */
 #include <gst/audio/audio.h>
@@ -25,7 +28,7 @@ GST_DEBUG_CATEGORY_STATIC (amd_ac_debug);
 #define AMD_AC_FORMATS "{ F64LE, F32LE, S32LE, S24_32LE, S24LE, S16LE, S8, U8, U32LE, U24_32LE, U24LE, S20LE, U20LE, S18LE, U18LE, U16LE, " \
     "F64BE, F32BE, S32BE, U32BE, S24_32BE, U24_32BE, S24BE, U24BE, S20BE, U20BE, S18BE, U18BE, S16BE, U16BE }"
 #define AMD_AC_CAPS "audio/x-raw, format = (string) " AMD_AC_FORMATS ", rate = (int) [ 1, MAX ], " \
-    "channels = (int) [ 1, 8 ], layout = (string) interleaved"
+    "channels = (int) [ 1, 8 ], layout = (string) { interleaved, non-interleaved }"
 
 static GstStaticPadTemplate ac_sink = GST_STATIC_PAD_TEMPLATE ("sink", GST_PAD_SINK, GST_PAD_ALWAYS, GST_STATIC_CAPS (AMD_AC_CAPS));
 static GstStaticPadTemplate ac_src = GST_STATIC_PAD_TEMPLATE ("src", GST_PAD_SRC, GST_PAD_ALWAYS, GST_STATIC_CAPS (AMD_AC_CAPS));
@@ -258,6 +261,9 @@ amd_ac_fixate_caps (GstBaseTransform * t, GstPadDirection direction, GstCaps * c
   outs = gst_caps_get_structure (result, 0);
   amd_ac_fixate_channels (ins, outs);
   amd_ac_fixate_format (ins, outs);
+  /* the input's layout where the peer leaves it open */
+  if (gst_structure_get_string (ins, "layout") && gst_structure_has_field (outs, "layout") && !gst_structure_get_string (outs, "layout"))
+    gst_structure_fixate_field_string (outs, "layout", gst_structure_get_string (ins, "layout"));
   return gst_caps_fixate (result);
 }
 
@@ -270,15 +276,21 @@ amd_ac_info (const GstAudioInfo * i, GstAmdAudioInfo * a)
   if (GST_AUDIO_INFO_FORMAT (i) < GST_AUDIO_FORMAT_S8 || GST_AUDIO_INFO_FORMAT (i) > GST_AUDIO_FORMAT_F64BE)
     return FALSE;
   a->format = (int32_t) GST_AUDIO_INFO_FORMAT (i);
-  if (GST_AUDIO_INFO_CHANNELS (i) > GSTAMD_AUDIO_MAX_CHANNELS || GST_AUDIO_INFO_LAYOUT (i) != GST_AUDIO_LAYOUT_INTERLEAVED)
+  if (GST_AUDIO_INFO_CHANNELS (i) > GSTAMD_AUDIO_MAX_CHANNELS)
     return FALSE;
   a->rate = GST_AUDIO_INFO_RATE (i);
   a->channels = GST_AUDIO_INFO_CHANNELS (i);
-  a->layout = 0;
+  a->layout = 0;                /* the layouts go to gstamd_audio_converter_new_layouts beside the infos (amd_ac_layout) */
   a->unpositioned = GST_AUDIO_INFO_IS_UNPOSITIONED (i) ? 1 : 0;
   for (c = 0; c < a->channels; c++)
     a->position[c] = (int32_t) i->position[c];          /* GstAudioChannelPosition values as they are */
   return TRUE;
+}
+
+static int
+amd_ac_layout (const GstAudioInfo * i)
+{
+  return GST_AUDIO_INFO_LAYOUT (i) == GST_AUDIO_LAYOUT_NON_INTERLEAVED ? GSTAMD_AUDIO_LAYOUT_NON_INTERLEAVED : GSTAMD_AUDIO_LAYOUT_INTERLEAVED;
 }
 
 /* gst_audio_convert_ensure_converter (gstaudioconvert.c:1590-1684): (re)make the converter for s->in / s->out with the element's current
@@ -335,7 +347,7 @@ amd_ac_ensure_converter (GstAmdAudioConvert * s)
     }
   }
   GST_OBJECT_UNLOCK (s);
-  s->conv = gstamd_audio_converter_new (0, &ai, &ao, &cfg, &status);
+  s->conv = gstamd_audio_converter_new_layouts (0, &ai, amd_ac_layout (&s->in), &ao, amd_ac_layout (&s->out), &cfg, &status);
   if (!s->conv) {
     GST_ERROR_OBJECT (s, "Failed to make converter (status %d): %s", status, gstamd_last_error ());
     return FALSE;
@@ -389,7 +401,11 @@ amd_ac_transform (GstBaseTransform * t, GstBuffer * inbuf, GstBuffer * outbuf)
   GstAmdAudioConvert *s = AMD_AC (t);
   GstMapInfo im, om;
   gsize frames;
-  gboolean ok = TRUE;
+  gboolean ok = TRUE, in_uploaded = FALSE;
+#if GST_CHECK_VERSION (1, 16, 0)
+  GstAudioMeta *in_meta = NULL;
+#endif
+  const gboolean out_planar = GST_AUDIO_INFO_LAYOUT (&s->out) == GST_AUDIO_LAYOUT_NON_INTERLEAVED;
 
   if (!amd_ac_ensure_converter (s))
     return GST_FLOW_NOT_NEGOTIATED;
@@ -400,6 +416,12 @@ amd_ac_transform (GstBaseTransform * t, GstBuffer * inbuf, GstBuffer * outbuf)
     gst_buffer_fill (outbuf, 0, im.data, im.size);
     gst_buffer_set_size (outbuf, im.size);
     gst_buffer_unmap (inbuf, &im);
+#if GST_CHECK_VERSION (1, 16, 0)
+    if (out_planar && !gst_buffer_get_audio_meta (outbuf)) {
+      GstAudioMeta *ameta = gst_buffer_get_audio_meta (inbuf);
+      gst_buffer_add_audio_meta (outbuf, &s->out, ameta ? ameta->samples : im.size / GST_AUDIO_INFO_BPF (&s->out), ameta ? ameta->offsets : NULL);
+    }
+#endif
     return GST_FLOW_OK;
   }
   if (!gst_buffer_map (inbuf, &im, GST_MAP_READ))
@@ -409,16 +431,36 @@ amd_ac_transform (GstBaseTransform * t, GstBuffer * inbuf, GstBuffer * outbuf)
     return GST_FLOW_ERROR;
   }
   frames = im.size / GST_AUDIO_INFO_BPF (&s->in);
+#if GST_CHECK_VERSION (1, 16, 0)
+  /* non-interleaved input: the frame count and the planes are what the buffer's GstAudioMeta says, as in gstamdaudioresample.c - a clipped
+   * buffer (gst_audio_buffer_clip / _truncate) keeps its size, moves offsets[] and lowers samples */
+  if (GST_AUDIO_INFO_LAYOUT (&s->in) == GST_AUDIO_LAYOUT_NON_INTERLEAVED && (in_meta = gst_buffer_get_audio_meta (inbuf)))
+    frames = in_meta->samples;
+#endif
   if (frames > om.size / GST_AUDIO_INFO_BPF (&s->out))
     frames = om.size / GST_AUDIO_INFO_BPF (&s->out);
   if (GST_BUFFER_FLAG_IS_SET (inbuf, GST_BUFFER_FLAG_GAP)) {
-    /* gstaudioconvert.c:1733-1747: a gap stays silence, the converter does not see it */
+    /* gstaudioconvert.c:1733-1747: a gap stays silence, the converter does not see it (silence is the same bytes in either layout) */
     gst_audio_format_fill_silence (s->out.finfo, om.data, frames * GST_AUDIO_INFO_BPF (&s->out));
   } else if (frames) {
     const gsize in_bytes = frames * GST_AUDIO_INFO_BPF (&s->in), out_bytes = frames * GST_AUDIO_INFO_BPF (&s->out);
     gst_amd_hip_select_device (s->device_id);
     ok = (s->stream || (s->stream = gstamd_stream_new ()) != NULL) && ac_staging (&s->d_in, &s->d_in_size, in_bytes) &&
-        ac_staging (&s->d_out, &s->d_out_size, out_bytes) && gstamd_device_upload_async (s->d_in, im.data, in_bytes, s->stream) == GSTAMD_OK &&
+        ac_staging (&s->d_out, &s->d_out_size, out_bytes);
+#if GST_CHECK_VERSION (1, 16, 0)
+    if (ok && in_meta) {
+      /* the planes are gathered back to back ([channels][frames]), which is how gstamd_audio_converter_samples takes a non-interleaved side */
+      const gsize plane = frames * (GST_AUDIO_INFO_BPF (&s->in) / GST_AUDIO_INFO_CHANNELS (&s->in));
+      gint c;
+      for (c = 0; ok && c < GST_AUDIO_INFO_CHANNELS (&s->in); c++)
+        ok = in_meta->offsets[c] <= im.size && plane <= im.size - in_meta->offsets[c] &&
+            gstamd_device_upload_async ((guint8 *) s->d_in + c * plane, im.data + in_meta->offsets[c], plane, s->stream) == GSTAMD_OK;
+      if (!ok)
+        GST_ERROR_OBJECT (s, "a plane of the buffer's GstAudioMeta lies outside the buffer, or its upload failed");
+      in_uploaded = TRUE;
+    }
+#endif
+    ok = ok && (in_uploaded || gstamd_device_upload_async (s->d_in, im.data, in_bytes, s->stream) == GSTAMD_OK) &&
         gstamd_audio_converter_samples (s->conv, 0, s->d_in, frames, s->d_out, frames, s->stream) == GSTAMD_OK &&
         gstamd_device_download_async (om.data, s->d_out, out_bytes, s->stream) == GSTAMD_OK && gstamd_stream_synchronize (s->stream) == GSTAMD_OK;
   }
@@ -429,6 +471,13 @@ amd_ac_transform (GstBaseTransform * t, GstBuffer * inbuf, GstBuffer * outbuf)
     return GST_FLOW_ERROR;
   }
   gst_buffer_set_size (outbuf, frames * GST_AUDIO_INFO_BPF (&s->out));
+#if GST_CHECK_VERSION (1, 16, 0)
+  /* a non-interleaved output: planes back to back + the GstAudioMeta that gst_audio_buffer_map requires for this layout */
+  if (out_planar && !gst_buffer_get_audio_meta (outbuf))
+    gst_buffer_add_audio_meta (outbuf, &s->out, frames, NULL);
+#else
+  (void) out_planar;
+#endif
   return GST_FLOW_OK;
 }
 
