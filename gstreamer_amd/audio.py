@@ -175,17 +175,26 @@ for _g, (_n, _bytes) in enumerate((("16", 2), ("24_32", 4), ("32", 4), ("24", 3)
 DITHER = {"none": 0, "rpdf": 1, "tpdf": 2, "tpdf-hf": 3}
 NOISE_SHAPING = {"none": 0, "error-feedback": 1, "simple": 2, "medium": 3, "high": 4}
 MAX_CHANNELS = 8
+MAX_CHANNELS_WIDE = 64      # gstamd_audio_converter_new_wide
 LAYOUT = {"interleaved": 0, "non-interleaved": 1}     # GstAudioLayout
 # default positions of gst_audio_info_set_format (audio-info.c: gst_audio_channel_positions ... default_channel_order) for 1 / 2 channels
 DEFAULT_POSITIONS = {1: [-2], 2: [0, 1]}
 # GstAudioChannelPosition (audio-channels.h:101-133)
 POSITION = {"none": -3, "mono": -2, "invalid": -1, "front-left": 0, "front-right": 1, "front-center": 2, "lfe1": 3, "rear-left": 4, "rear-right": 5,
-            "front-left-of-center": 6, "front-right-of-center": 7, "rear-center": 8, "lfe2": 9, "side-left": 10, "side-right": 11}
+            "front-left-of-center": 6, "front-right-of-center": 7, "rear-center": 8, "lfe2": 9, "side-left": 10, "side-right": 11,
+            "top-front-left": 12, "top-front-right": 13, "top-front-center": 14, "top-center": 15, "top-rear-left": 16, "top-rear-right": 17,
+            "top-side-left": 18, "top-side-right": 19, "top-rear-center": 20}
 
 
 class AudioInfo(C.Structure):
     _fields_ = [("format", C.c_int32), ("rate", C.c_int32), ("channels", C.c_int32), ("layout", C.c_int32), ("unpositioned", C.c_int32),
                 ("position", C.c_int32 * MAX_CHANNELS)]
+
+
+class AudioInfoWide(C.Structure):
+    """GstAmdAudioInfoWide: AudioInfo with 64 positions"""
+    _fields_ = [("format", C.c_int32), ("rate", C.c_int32), ("channels", C.c_int32), ("layout", C.c_int32), ("unpositioned", C.c_int32),
+                ("position", C.c_int32 * MAX_CHANNELS_WIDE)]
 
 
 class AudioConverterConfig(C.Structure):
@@ -206,6 +215,27 @@ def audio_info(fmt, rate, channels, positions=None, unpositioned=False):
     return ai
 
 
+def audio_info_wide(fmt, rate, channels, positions=None, unpositioned=False):
+    """audio_info for up to 64 channels (channel counts outside 1 .. 64 are passed through for the constructor to refuse)"""
+    ai = AudioInfoWide()
+    ai.format, ai.rate, ai.channels, ai.layout, ai.unpositioned = AFMT[fmt], rate, channels, 0, int(unpositioned)
+    pos = positions if positions is not None else DEFAULT_POSITIONS.get(channels)
+    if pos is None:
+        pos = [POSITION["none"]] * max(0, min(channels, MAX_CHANNELS_WIDE))
+        ai.unpositioned = 1
+    for i, v in enumerate(pos):
+        ai.position[i] = POSITION[v] if isinstance(v, str) else v
+    return ai
+
+
+def wide_matrix(mix_matrix):
+    """a [out][in] matrix as the flat float array gstamd_audio_converter_new_wide takes (None stays None)"""
+    if mix_matrix is None:
+        return None
+    flat = [float(v) for row in mix_matrix for v in row]
+    return (C.c_float * len(flat))(*flat)
+
+
 _conv_ready = False
 
 
@@ -219,6 +249,9 @@ def _conv_lib():
         L.gstamd_audio_converter_new_layouts.restype = C.c_void_p
         L.gstamd_audio_converter_new_layouts.argtypes = [C.c_int, C.POINTER(AudioInfo), C.c_int, C.POINTER(AudioInfo), C.c_int,
                                                          C.POINTER(AudioConverterConfig), C.POINTER(C.c_int)]
+        L.gstamd_audio_converter_new_wide.restype = C.c_void_p
+        L.gstamd_audio_converter_new_wide.argtypes = [C.c_int, C.POINTER(AudioInfoWide), C.c_int, C.POINTER(AudioInfoWide), C.c_int,
+                                                      C.POINTER(AudioConverterConfig), C.POINTER(C.c_float), C.POINTER(C.c_int)]
         L.gstamd_audio_converter_samples_planes.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_void_p), C.c_size_t,
                                                             C.c_void_p]
         L.gstamd_audio_converter_free.argtypes = [C.c_void_p]
@@ -303,3 +336,17 @@ class AudioConverter:
         if self._h:
             _conv_lib().gstamd_audio_converter_free(self._h)
             self._h = None
+
+
+class AudioConverterWide(AudioConverter):
+    """gstamd_audio_converter_new_wide: AudioInfoWide infos of 1 .. 64 channels, the layouts, and the mix matrix ([out][in] rows, None for the
+    default one) as an argument of its own - config.has_mix_matrix stays 0.  Every method of AudioConverter works on it."""
+
+    def __init__(self, in_info, out_info, config=None, flags=0, in_layout=0, out_layout=0, mix_matrix=None):
+        st = C.c_int(0)
+        lay = [LAYOUT[v] if isinstance(v, str) else int(v or 0) for v in (in_layout, out_layout)]
+        self._h = _conv_lib().gstamd_audio_converter_new_wide(flags, C.byref(in_info) if in_info is not None else None, lay[0],
+                                                              C.byref(out_info) if out_info is not None else None, lay[1],
+                                                              C.byref(config) if config is not None else None, wide_matrix(mix_matrix), C.byref(st))
+        if not self._h:
+            raise _v.GstAmdError(st.value, _v.last_error())

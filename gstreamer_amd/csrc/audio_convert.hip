@@ -95,10 +95,49 @@ __global__ __launch_bounds__ (64) void k_aconv_shape_planes (AConvPlan p, const 
     aconv_shape_planes<K> (p, qv, qd, hist, dst);
 }
 
+// ---- the wide converter (gstamd_audio_converter_new_wide) ----------------------------------------------------------------
+// Its unmixed interleaved sides go through k_aconv_pre / k_aconv_post / k_aconv_shape above, which never look at a channel count beyond
+// p.out_ch / p.q_stride.  The first kernel of every other case - a mix, a non-interleaved input - is this one: blockIdx.x is a tile of
+// `tile` frames, staged once into LDS with the matrix and mixed from there (audio_convert_device.h).
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_wide_mix (AConvPlan p, AConvWideMatrix w, AConvPlanesWide src, int in_planar, uint8_t *__restrict__ mid, int tile)
+{
+  extern __shared__ __attribute__ ((aligned (16))) unsigned char aconv_wide_lds[];
+  const size_t n0 = (size_t) blockIdx.x * (size_t) tile;
+  if (n0 >= src.frames)
+    return;
+  const int nf = src.frames - n0 < (size_t) tile ? (int) (src.frames - n0) : tile;
+  uint8_t *x = aconv_wide_lds, *mat = aconv_wide_lds + aconv_wide_x_bytes (p, tile);
+  if (p.mix)
+    aconv_wide_stage_matrix (p, w, mat, (int) threadIdx.x, 256);
+  aconv_wide_stage_lane<K> (p, src, in_planar, n0, nf, x, (int) threadIdx.x, 256);
+  __syncthreads ();
+  aconv_wide_mix_lane (p, x, mat, w.use, mid, n0, nf, (int) threadIdx.x, 256);
+}
+
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_wide_post_planes (AConvPlan p, const AConvJump *__restrict__ jump, AConvDitherState ds, const uint8_t *__restrict__ mid,
+    AConvPlanesWide dst, int32_t *__restrict__ qv, int32_t *__restrict__ qd)
+{
+  aconv_post_lane_planes_of<K> (p, *jump, ds, mid, dst, qv, qd, (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+template <int K>
+__global__ __launch_bounds__ (64) void k_aconv_wide_shape_planes (AConvPlan p, const int32_t *__restrict__ qv, const int32_t *__restrict__ qd, int32_t *__restrict__ hist,
+    AConvPlanesWide dst)
+{
+  if (threadIdx.x == 0)
+    aconv_shape_planes_of<K> (p, qv, qd, hist, dst);
+}
+
 static unsigned aconv_blocks (const AConvSplit &s) { return (unsigned) ((aconv_split_lanes (s) + 255) / 256); }
 
 struct GstAmdAudioConverter {
-  GstAmdAudioInfo in, out;
+  GstAmdAudioInfo in, out;                              /* (not of a wide converter) */
+  bool wide = false;                                    /* made by gstamd_audio_converter_new_wide: plan is wide_plan.s, the matrices are in device memory */
+  AConvWidePlan wide_plan;
+  AConvWideMatrix wide_dev = { nullptr, nullptr, nullptr };
+  size_t hist_bytes = sizeof (int32_t) * 8 * GSTAMD_AUDIO_MAX_CHANNELS;
   GstAmdAudioConverterConfig cfg;
   int flags = 0;
   int in_layout = 0, out_layout = 0;                    /* GSTAMD_AUDIO_LAYOUT_* of the two sides */
@@ -114,6 +153,46 @@ struct GstAmdAudioConverter {
   uint8_t *mid_a = nullptr, *mid_b = nullptr;           /* before / after the resampler */
   size_t mid_a_size = 0, mid_b_size = 0;
 };
+
+// what the two constructors share once the plan stands: the resampler, the jump table, the error history
+static GstAmdAudioConverter *aconv_finish_new (GstAmdAudioConverter *c, bool resample, int in_rate, int out_rate, int *status)
+{
+  const GstAmdAudioConverterConfig &cfg = c->cfg;
+  if (resample) {
+    GstAmdAudioResamplerOptions ro;
+    if (cfg.has_resampler_options)
+      ro = cfg.resampler_options;
+    else
+      gstamd_audio_resampler_options_init (&ro);        /* the converter hands its (empty) config to the resampler: every key at its default */
+    int st = 0;
+    c->resampler = gstamd_audio_resampler_new (cfg.resampler_method, (c->flags & 2) ? 4 : 0, c->plan.mid_in, c->plan.out_ch, in_rate, out_rate, &ro, &st);
+    if (!c->resampler) {
+      gstamd_audio_converter_free (c);
+      if (status)
+        *status = st;
+      return nullptr;
+    }
+  }
+  auto fail = [&](const char *msg) -> GstAmdAudioConverter * {
+    gstamd_audio_converter_free (c);
+    const int code = aconv_fail (GSTAMD_ERR_HIP, msg);
+    if (status)
+      *status = code;
+    return nullptr;
+  };
+  aconv_make_jump (&c->jump_host);
+  if (hipMalloc ((void **) &c->jump_dev, sizeof (AConvJump)) != hipSuccess ||
+      hipMemcpy (c->jump_dev, &c->jump_host, sizeof (AConvJump), hipMemcpyHostToDevice) != hipSuccess)
+    return fail ("jump table upload");
+  if (c->plan.ns) {
+    /* (a null-stream memset returns before it has run and is not ordered against a non-blocking stream: wait for it - audio_kernels.hip ensure_hist) */
+    if (hipMalloc ((void **) &c->hist, c->hist_bytes) != hipSuccess || hipMemset (c->hist, 0, c->hist_bytes) != hipSuccess || hipDeviceSynchronize () != hipSuccess)
+      return fail ("error history");
+  }
+  if (status)
+    *status = GSTAMD_OK;
+  return c;
+}
 
 extern "C" {
 
@@ -166,38 +245,59 @@ GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAm
     delete c;
     return fail (code, err);
   }
-  if (resample) {
-    GstAmdAudioResamplerOptions ro;
-    if (cfg.has_resampler_options)
-      ro = cfg.resampler_options;
+  return aconv_finish_new (c, resample, in->rate, out->rate, status);
+}
+
+GstAmdAudioConverter *gstamd_audio_converter_new_wide (int flags, const GstAmdAudioInfoWide *in, int in_layout, const GstAmdAudioInfoWide *out, int out_layout,
+    const GstAmdAudioConverterConfig *config, const float *mix_matrix, int *status)
+{
+  auto fail = [&](int code, const std::string &msg) -> GstAmdAudioConverter * {
+    if (status)
+      *status = aconv_fail (code, msg);
     else
-      gstamd_audio_resampler_options_init (&ro);        /* the converter hands its (empty) config to the resampler: every key at its default */
-    int st = 0;
-    c->resampler = gstamd_audio_resampler_new (cfg.resampler_method, (flags & 2) ? 4 : 0, c->plan.mid_in, out->channels, in->rate, out->rate, &ro, &st);
-    if (!c->resampler) {
-      delete c;
-      if (status)
-        *status = st;
-      return nullptr;
-    }
+      aconv_fail (code, msg);
+    return nullptr;
+  };
+  if (!in || !out)
+    return fail (GSTAMD_ERR_INVALID, "NULL info");
+  GstAmdAudioConverterConfig cfg;
+  if (config)
+    cfg = *config;
+  else
+    gstamd_audio_converter_config_init (&cfg);
+  GstAmdAudioConverter *c = new GstAmdAudioConverter ();
+  memset (&c->in, 0, sizeof (c->in));
+  memset (&c->out, 0, sizeof (c->out));
+  c->wide = true;
+  c->cfg = cfg;
+  c->flags = flags;
+  c->in_layout = in_layout;
+  c->out_layout = out_layout;
+  c->hist_bytes = sizeof (int32_t) * 8 * GSTAMD_AUDIO_MAX_CHANNELS_WIDE;
+  bool resample = false;
+  std::string err;
+  const int code = aconv_make_plan_wide (flags, in, in_layout, out, out_layout, cfg, mix_matrix, &c->wide_plan, &resample, &c->passthrough, &err);
+  if (code != GSTAMD_OK) {
+    delete c;
+    return fail (code, err);
   }
-  aconv_make_jump (&c->jump_host);
-  if (hipMalloc ((void **) &c->jump_dev, sizeof (AConvJump)) != hipSuccess ||
-      hipMemcpy (c->jump_dev, &c->jump_host, sizeof (AConvJump), hipMemcpyHostToDevice) != hipSuccess) {
+  c->plan = c->wide_plan.s;
+  /* the matrices: uploaded once, freed in _free */
+  const size_t n = c->wide_plan.m.size ();
+  float *m = nullptr;
+  int32_t *mi = nullptr;
+  uint64_t *use = nullptr;
+  const bool up = hipMalloc ((void **) &m, 4 * n) == hipSuccess && hipMalloc ((void **) &mi, 4 * n) == hipSuccess &&
+      hipMalloc ((void **) &use, 8 * GSTAMD_AUDIO_MAX_CHANNELS_WIDE) == hipSuccess &&
+      hipMemcpy (m, c->wide_plan.m.data (), 4 * n, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy (mi, c->wide_plan.mi.data (), 4 * n, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy (use, c->wide_plan.use.data (), 8 * GSTAMD_AUDIO_MAX_CHANNELS_WIDE, hipMemcpyHostToDevice) == hipSuccess;
+  c->wide_dev = { m, mi, use };
+  if (!up) {
     gstamd_audio_converter_free (c);
-    return fail (GSTAMD_ERR_HIP, "jump table upload");
+    return fail (GSTAMD_ERR_HIP, "mix matrix upload");
   }
-  if (c->plan.ns) {
-    const size_t hb = sizeof (int32_t) * 8 * GSTAMD_AUDIO_MAX_CHANNELS;
-    /* (a null-stream memset returns before it has run and is not ordered against a non-blocking stream: wait for it - audio_kernels.hip ensure_hist) */
-    if (hipMalloc ((void **) &c->hist, hb) != hipSuccess || hipMemset (c->hist, 0, hb) != hipSuccess || hipDeviceSynchronize () != hipSuccess) {
-      gstamd_audio_converter_free (c);
-      return fail (GSTAMD_ERR_HIP, "error history");
-    }
-  }
-  if (status)
-    *status = GSTAMD_OK;
-  return c;
+  return aconv_finish_new (c, resample, in->rate, out->rate, status);
 }
 
 void gstamd_audio_converter_free (GstAmdAudioConverter *c)
@@ -218,6 +318,12 @@ void gstamd_audio_converter_free (GstAmdAudioConverter *c)
     (void) hipFree (c->q_v);
   if (c->q_d)
     (void) hipFree (c->q_d);
+  if (c->wide_dev.m)
+    (void) hipFree ((void *) c->wide_dev.m);
+  if (c->wide_dev.mi)
+    (void) hipFree ((void *) c->wide_dev.mi);
+  if (c->wide_dev.use)
+    (void) hipFree ((void *) c->wide_dev.use);
   delete c;
 }
 
@@ -229,7 +335,7 @@ void gstamd_audio_converter_reset (GstAmdAudioConverter *c)
     gstamd_audio_resampler_reset (c->resampler);
   if (c && c->hist) {
     (void) hipDeviceSynchronize ();
-    (void) hipMemset (c->hist, 0, sizeof (int32_t) * 8 * GSTAMD_AUDIO_MAX_CHANNELS);
+    (void) hipMemset (c->hist, 0, c->hist_bytes);
     (void) hipDeviceSynchronize ();
   }
 }
@@ -256,10 +362,10 @@ int gstamd_audio_converter_get_mix_matrix (GstAmdAudioConverter *c, float *matri
   if (!c || !matrix)
     return -1;
   int n = 0;
-  for (int ci = 0; ci < c->in.channels; ci++)
-    for (int co = 0; co < c->out.channels; co++, n++)
+  for (int ci = 0; ci < c->plan.in_ch; ci++)
+    for (int co = 0; co < c->plan.out_ch; co++, n++)
       if (n < max)
-        matrix[n] = c->plan.m[ci][co];
+        matrix[n] = c->wide ? c->wide_plan.m[(size_t) ci * (size_t) c->plan.out_ch + (size_t) co] : c->plan.m[ci][co];
   return n;
 }
 
@@ -335,7 +441,21 @@ static int aconv_run (GstAmdAudioConverter *c, uint8_t *const *in, size_t in_fra
   if (in) {
     if ((r = ensure (&c->mid_a, &c->mid_a_size, (in_frames ? in_frames : 1) * mid_bytes_in)) != GSTAMD_OK)
       return r;
-    if (c->in_layout) {
+    if (c->wide && (c->in_layout || p.mix)) {
+      AConvPlanesWide src;
+      memset (&src, 0, sizeof (src));
+      for (int ci = 0; ci < (c->in_layout ? p.in_ch : 1); ci++)
+        src.p[ci] = in[ci];
+      src.frames = in_frames;
+      const int tile = aconv_wide_tile_frames (p.in_ch, p.out_ch);
+      const size_t lds = aconv_wide_lds_bytes (p, tile);        /* at most 256 * 9 * 8 + 4 * 64 bytes of samples, 16 KB of matrix */
+      if (in_frames) {
+#define PRE(K) k_aconv_wide_mix<K><<<dim3 ((unsigned) ((in_frames + (size_t) tile - 1) / (size_t) tile)), dim3 (256), lds, stream>>> (p, c->wide_dev, src, c->in_layout, \
+    c->mid_a, tile)
+        GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+      }
+    } else if (c->in_layout) {
       AConvPlanes src;
       memset (&src, 0, sizeof (src));
       for (int ci = 0; ci < p.in_ch; ci++)
@@ -379,7 +499,24 @@ static int aconv_run (GstAmdAudioConverter *c, uint8_t *const *in, size_t in_fra
     if ((r = ensure (&c->q_v, &c->q_v_size, samples * 4)) != GSTAMD_OK || (r = ensure (&c->q_d, &c->q_d_size, samples * 4)) != GSTAMD_OK)
       return r;
   }
-  if (c->out_layout) {
+  if (c->out_layout && c->wide) {
+    AConvPlanesWide dst;
+    memset (&dst, 0, sizeof (dst));
+    for (int co = 0; co < p.out_ch; co++)
+      dst.p[co] = out[co];
+    dst.frames = out_frames;
+    aconv_planes_heads_wide (&dst, p.out_ch, (int) out_b, aconv_post_grouped (p));
+    const size_t lanes = aconv_planes_lanes_wide (dst, p.out_ch);
+#define POST(K) k_aconv_wide_post_planes<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch), dim3 (256), 0, stream>>> (p, c->jump_dev, c->dither, after, dst, \
+    (int32_t *) c->q_v, (int32_t *) c->q_d)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+    if (shape) {
+#define SHAPE(K) k_aconv_wide_shape_planes<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, (const int32_t *) c->q_v, (const int32_t *) c->q_d, c->hist, dst)
+      GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+    }
+  } else if (c->out_layout) {
     AConvPlanes dst;
     memset (&dst, 0, sizeof (dst));
     for (int co = 0; co < p.out_ch; co++)
@@ -423,7 +560,7 @@ int gstamd_audio_converter_samples_planes (GstAmdAudioConverter *c, int flags, c
     return aconv_fail (GSTAMD_ERR_INVALID, "NULL converter or output");
   if (in_frames == 0)                           /* gst_audio_converter_samples :1618-1621: "skipping empty buffer" */
     return GSTAMD_OK;
-  uint8_t *ip[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr }, *op[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr };
+  uint8_t *ip[GSTAMD_AUDIO_MAX_CHANNELS_WIDE] = { nullptr }, *op[GSTAMD_AUDIO_MAX_CHANNELS_WIDE] = { nullptr };
   for (int k = 0; in && k < (c->in_layout ? c->plan.in_ch : 1); k++)
     if (!(ip[k] = (uint8_t *) in[k]))
       return aconv_fail (GSTAMD_ERR_INVALID, "NULL input plane");
@@ -441,7 +578,7 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
   if (in_frames == 0)
     return GSTAMD_OK;
   /* a non-interleaved side as gstamd_audio_resampler_resample takes it: the channels one after the other, in_frames (out_frames) samples apart */
-  uint8_t *ip[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr }, *op[GSTAMD_AUDIO_MAX_CHANNELS] = { nullptr };
+  uint8_t *ip[GSTAMD_AUDIO_MAX_CHANNELS_WIDE] = { nullptr }, *op[GSTAMD_AUDIO_MAX_CHANNELS_WIDE] = { nullptr };
   const size_t in_plane = in_frames * (size_t) afmt_bytes (c->plan.in_fmt), out_plane = out_frames * (size_t) afmt_bytes (c->plan.out_fmt);
   for (int k = 0; in && k < (c->in_layout ? c->plan.in_ch : 1); k++)
     ip[k] = (uint8_t *) in + (size_t) k * in_plane;

@@ -63,6 +63,14 @@ struct AConvPlanes {
   uint8_t realign;
 };
 
+// the same for a converter of up to 64 channels (gstamd_audio_converter_new_wide); 592 bytes of kernel arguments
+struct AConvPlanesWide {
+  uint8_t *p[GSTAMD_AUDIO_MAX_CHANNELS_WIDE];
+  size_t frames;
+  uint8_t head[GSTAMD_AUDIO_MAX_CHANNELS_WIDE];
+  uint8_t realign;              // 0: the wide first kernel stages every plane on its own, nothing has to line up
+};
+
 GSTAMD_AC int amid_bytes (int mid) { return mid == AMID_S16 ? 2 : mid == AMID_F64 ? 8 : 4; }
 
 // ---- the raw GstAudioFormats, values 2 .. 31 (audio-format.h:80-130) --------------------------------------------------------------------------------
@@ -900,7 +908,7 @@ template <int K> GSTAMD_AC void aconv_post_lane (const AConvPlan &p, const AConv
 
 // ---- a non-interleaved side: row y of a launch is a plane, its lanes take four consecutive frames of it on aligned dwords (the unpack /
 // pack bodies above as they are) or one frame; what is strided is the interleaved mid buffer ---------------------------------------
-GSTAMD_AC AConvSplit aconv_plane_split (const AConvPlanes &pl, int y)
+template <class PL> GSTAMD_AC AConvSplit aconv_plane_split_of (const PL &pl, int y)
 {
   AConvSplit s = { 0, 0, pl.frames };
   if (pl.realign) {                     /* (frames >= 12: aconv_planes_heads) */
@@ -912,6 +920,8 @@ GSTAMD_AC AConvSplit aconv_plane_split (const AConvPlanes &pl, int y)
   }
   return s;
 }
+
+GSTAMD_AC AConvSplit aconv_plane_split (const AConvPlanes &pl, int y) { return aconv_plane_split_of (pl, y); }
 
 // the first kernel: lane t of output channel co.  The mixer's sums run over the input planes in ascending order as in aconv_pre_sample_at;
 // a four-frame lane reads B dwords of every plane it uses - aligned ones where all planes reach a dword boundary at the same frame
@@ -966,11 +976,11 @@ template <int K> GSTAMD_AC void aconv_pre_lane_planes (const AConvPlan &p, const
     aconv_pre_group_planes<K, false> (p, src, mid, co, s.head + 4 * t);
 }
 
-// the second kernel: lane t of output plane c
-template <int K> GSTAMD_AC void aconv_post_lane_planes (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, const AConvPlanes &dst,
-    int32_t *qv, int32_t *qd, int c, size_t t)
+// the second kernel: lane t of output plane c (PL: AConvPlanes or AConvPlanesWide)
+template <int K, class PL> GSTAMD_AC void aconv_post_lane_planes_of (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid,
+    const PL &dst, int32_t *qv, int32_t *qd, int c, size_t t)
 {
-  const AConvSplit s = aconv_plane_split (dst, c);
+  const AConvSplit s = aconv_plane_split_of (dst, c);
   if (t >= aconv_split_lanes (s))
     return;
   constexpr int B = akind_bytes (K);
@@ -1018,12 +1028,23 @@ template <int K> GSTAMD_AC void aconv_post_lane_planes (const AConvPlan &p, cons
   }
 }
 
+template <int K> GSTAMD_AC void aconv_post_lane_planes (const AConvPlan &p, const AConvJump &jump, const AConvDitherState &ds, const uint8_t *mid, const AConvPlanes &dst,
+    int32_t *qv, int32_t *qd, int c, size_t t)
+{
+  aconv_post_lane_planes_of<K> (p, jump, ds, mid, dst, qv, qd, c, t);
+}
+
 // noise shaping into a non-interleaved output: ONE recurrence over plane 0, plane 1, ... of the call (the plan's q_stride is 1, the
 // history one channel's, carried from each plane into the next)
-template <int K> GSTAMD_AC void aconv_shape_planes (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, const AConvPlanes &dst)
+template <int K, class PL> GSTAMD_AC void aconv_shape_planes_of (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, const PL &dst)
 {
   for (int c = 0; c < p.out_ch; c++)
     aconv_shape_channel<K> (p, v + (size_t) c * dst.frames, d + (size_t) c * dst.frames, hist, dst.p[c], dst.frames, 0);
+}
+
+template <int K> GSTAMD_AC void aconv_shape_planes (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, const AConvPlanes &dst)
+{
+  aconv_shape_planes_of<K> (p, v, d, hist, dst);
 }
 
 // head[] of a launch's rows (host).  rows_are_planes: row y works on plane y alone (the second kernel; the first one without a mix);
@@ -1058,6 +1079,221 @@ inline size_t aconv_planes_lanes (const AConvPlanes &pl, int rows)
 GSTAMD_AC bool aconv_pre_grouped_planes (const AConvPlan &p) { return p.mid_in == AMID_S32 || p.mid_in == AMID_F64; }
 // ... and on interleaved frames whose layout changes (aconv_pre_lane_mix; the mixer between two interleaved sides keeps its lane per sample)
 GSTAMD_AC bool aconv_pre_grouped_mix (const AConvPlan &p) { return p.mix && (p.mid_in == AMID_S32 || p.mid_in == AMID_F64); }
+
+// ---- the wide converter's mixing first kernel (1 .. 64 channels) -------------------------------------------------------
+// A workgroup takes a tile of frames.  Phase 1 (aconv_wide_stage_lane, aconv_wide_stage_matrix): every input sample of the tile is unpacked
+// ONCE into LDS, in the mid_in format - x[frame][channel], 4-byte slots (S16 widened, S32, F32) or 8-byte ones (F64), rows of in_ch | 1
+// slots - and the matrix (mi for the integer formats, m for the float ones: 4-byte entries either way) is copied beside it as it lies in
+// device memory, [in][out] with rows of out_ch.  Phase 2 after the barrier (aconv_wide_mix_lane): lane -> (frame, output channel), the
+// output channel running fastest, and the sums of aconv_pre_sample_at: input channels ascending, one accumulator from zero, the product
+// rounded and then added, only the channels of use[co].  What the lanes of a wave read then is one x slot broadcast (or, with few output
+// channels, rows in_ch | 1 slots apart: an odd stride meets every bank once) and consecutive matrix entries.
+struct AConvWideMatrix {        // device memory, owned by the converter
+  const float *m;               // [in][out], row stride out_ch
+  const int32_t *mi;
+  const uint64_t *use;          // [out]: bit ci = input channel ci takes part
+};
+
+typedef uint64_t __attribute__ ((may_alias)) aconv_u64;
+typedef uint16_t __attribute__ ((may_alias)) aconv_u16;
+
+// frames of a tile: about 2048 samples of the wider side, a multiple of four (so every tile starts at the buffer's byte phase), 32 .. 256
+GSTAMD_AC int aconv_wide_tile_frames (int in_ch, int out_ch)
+{
+  const int t = (2048 / (in_ch > out_ch ? in_ch : out_ch)) & ~3;
+  return t < 32 ? 32 : (t > 256 ? 256 : t);
+}
+GSTAMD_AC int aconv_wide_x_stride (const AConvPlan &p) { return p.in_ch | 1; }
+GSTAMD_AC size_t aconv_wide_x_bytes (const AConvPlan &p, int tile) { return (size_t) (p.mid_in == AMID_F64 ? 8 : 4) * (size_t) tile * (size_t) aconv_wide_x_stride (p); }
+GSTAMD_AC size_t aconv_wide_lds_bytes (const AConvPlan &p, int tile) { return aconv_wide_x_bytes (p, tile) + (p.mix ? 4 * (size_t) p.in_ch * (size_t) p.out_ch : 0); }
+
+// aconv_split for a run of n samples inside a tile, on the device
+GSTAMD_AC AConvSplit aconv_wide_split (const uint8_t *q, int bytes, size_t n)
+{
+  AConvSplit s = { 0, 0, n };
+  size_t h = 0;
+  while (h < 4 && (((uintptr_t) q + (size_t) bytes * h) & 3u))
+    h++;
+  if (h == 4 || n < h + 4)
+    return s;
+  s.head = h;
+  s.groups = (n - h) / 4;
+  return s;
+}
+
+GSTAMD_AC void aconv_wide_put32 (uint8_t *x, size_t e, uint32_t v) { ((aconv_u32 *) x)[e] = v; }
+GSTAMD_AC void aconv_wide_put64 (uint8_t *x, size_t e, uint64_t v) { ((aconv_u64 *) x)[e] = v; }
+
+// one sample at q into slot e
+template <int K> GSTAMD_AC void aconv_wide_stage1 (const AConvPlan &p, const uint8_t *q, uint8_t *x, size_t e)
+{
+  switch (p.mid_in) {
+    case AMID_S16: {
+      int16_t v; memcpy (&v, q, 2);
+      aconv_wide_put32 (x, e, (uint32_t) (int32_t) v);
+      break;
+    }
+    case AMID_S32: aconv_wide_put32 (x, e, (uint32_t) aconv_unpack_int<K> (p, q, 0)); break;
+    case AMID_F32: {
+      uint32_t v; memcpy (&v, q, 4);
+      aconv_wide_put32 (x, e, v);
+      break;
+    }
+    default:
+      aconv_wide_put64 (x, e, d_bits (p.convert_in ? aconv_s32_to_double (aconv_unpack_int<K> (p, q, 0)) : aconv_unpack_flt<K> (q, 0)));
+      break;
+  }
+}
+
+// four consecutive samples on aligned dwords at q into the slots e[0 .. 3]
+template <int K> GSTAMD_AC void aconv_wide_stage4 (const AConvPlan &p, const uint8_t *q, uint8_t *x, const size_t e[4])
+{
+  if (p.mid_in == AMID_F64) {
+    double r[4];
+    aconv_unpack4_f64<K> (p, q, r);
+    for (int j = 0; j < 4; j++)
+      aconv_wide_put64 (x, e[j], d_bits (r[j]));
+    return;
+  }
+  if constexpr (akind_bytes (K) <= 4) {
+    uint32_t w[4];
+    aconv_load4<K> (q, w);
+    for (int j = 0; j < 4; j++)
+      aconv_wide_put32 (x, e[j], p.mid_in == AMID_S32 ? (uint32_t) aconv_w_to_s32 (p, w[j]) : p.mid_in == AMID_S16 ? (uint32_t) (int32_t) (int16_t) w[j] : w[j]);
+  }
+}
+
+// phase 1: the tile's frames n0 .. n0 + nf - 1 into x.  in_planar: src.p[ci] are the planes, otherwise src.p[0] holds interleaved frames.
+// A run - the tile's samples of a plane, or all of them for interleaved frames - is split like a launch of the unmixed kernels: single
+// samples up to the first dword a sample starts on, lanes of four samples on aligned dwords, single ones again.
+template <int K> GSTAMD_AC void aconv_wide_stage_lane (const AConvPlan &p, const AConvPlanesWide &src, int in_planar, size_t n0, int nf, uint8_t *x, int tid, int nthreads)
+{
+  constexpr int B = akind_bytes (K);
+  const size_t xs = (size_t) aconv_wide_x_stride (p), ich = (size_t) p.in_ch;
+  const size_t runs = in_planar ? ich : 1, count = in_planar ? (size_t) nf : (size_t) nf * ich;
+  for (size_t t = (size_t) tid; t < runs * count; t += (size_t) nthreads) {
+    const size_t b = t / count, k = t % count;
+    const uint8_t *base = in_planar ? src.p[b] + (size_t) B * n0 : src.p[0] + (size_t) B * n0 * ich;
+    const AConvSplit s = aconv_wide_split (base, B, count);
+    if (k >= aconv_split_lanes (s))
+      continue;
+    if (k >= s.groups) {
+      const size_t i = aconv_split_single (s, k);
+      aconv_wide_stage1<K> (p, base + (size_t) B * i, x, in_planar ? i * xs + b : (i / ich) * xs + i % ich);
+      continue;
+    }
+    const size_t i = s.head + 4 * k;
+    size_t e[4];
+    for (int j = 0; j < 4; j++)
+      e[j] = in_planar ? (i + (size_t) j) * xs + b : ((i + (size_t) j) / ich) * xs + (i + (size_t) j) % ich;
+    aconv_wide_stage4<K> (p, base + (size_t) B * i, x, e);
+  }
+}
+
+// the matrix the mixer of this plan reads, as dwords
+GSTAMD_AC const uint32_t *aconv_wide_matrix_of (const AConvPlan &p, const AConvWideMatrix &w)
+{
+  return p.mid_in == AMID_S16 || p.mid_in == AMID_S32 ? (const uint32_t *) w.mi : (const uint32_t *) w.m;
+}
+
+GSTAMD_AC void aconv_wide_stage_matrix (const AConvPlan &p, const AConvWideMatrix &w, uint8_t *mat, int tid, int nthreads)
+{
+  const aconv_u32 *src = (const aconv_u32 *) aconv_wide_matrix_of (p, w);
+  for (int i = tid; i < p.in_ch * p.out_ch; i += nthreads)
+    aconv_wide_put32 (mat, (size_t) i, src[i]);
+}
+
+// phase 2: (frame f, output channel co) of the tile -> the interleaved mid buffer
+GSTAMD_AC void aconv_wide_mix_lane (const AConvPlan &p, const uint8_t *x, const uint8_t *mat, const uint64_t *use_of, uint8_t *mid, size_t n0, int nf, int tid, int nthreads)
+{
+  const size_t xs = (size_t) aconv_wide_x_stride (p), och = (size_t) p.out_ch;
+  const aconv_u32 *mw = (const aconv_u32 *) mat;
+  for (size_t o = (size_t) tid; o < (size_t) nf * och; o += (size_t) nthreads) {
+    const size_t f = o / och, co = o % och, oi = (n0 + f) * och + co;
+    const aconv_u32 *x4 = (const aconv_u32 *) x + f * xs;
+    const aconv_u64 *x8 = (const aconv_u64 *) x + f * xs;
+    const uint64_t use = p.mix ? use_of[co] : 0;
+    switch (p.mid_in) {
+      case AMID_S16: {
+        int32_t res;
+        if (!p.mix) {
+          res = (int32_t) x4[co];
+        } else {
+          uint32_t acc = 0;                     /* the reference's gint32, which wraps */
+          for (int ci = 0; ci < p.in_ch; ci++)
+            if ((use >> ci) & 1u)
+              acc += x4[ci] * mw[(size_t) ci * och + co];
+          res = (int32_t) (acc + 512u) >> 10;
+          res = res > 32767 ? 32767 : (res < -32768 ? -32768 : res);
+        }
+        ((aconv_u16 *) mid)[oi] = (uint16_t) (int16_t) res;
+        break;
+      }
+      case AMID_S32: {
+        int32_t r;
+        if (!p.mix) {
+          r = (int32_t) x4[co];
+        } else {
+          int64_t res = 0;
+          for (int ci = 0; ci < p.in_ch; ci++)
+            if ((use >> ci) & 1u)
+              res += (int64_t) (int32_t) x4[ci] * (int64_t) (int32_t) mw[(size_t) ci * och + co];
+          r = aconv_mix_round_s32 (res);
+        }
+        ((aconv_u32 *) mid)[oi] = (uint32_t) r;
+        break;
+      }
+      case AMID_F32: {
+        uint32_t rw;
+        if (!p.mix) {
+          rw = x4[co];
+        } else {
+          float r = 0.0f;
+          for (int ci = 0; ci < p.in_ch; ci++)
+            if ((use >> ci) & 1u)
+              r += bits_f (x4[ci]) * bits_f (mw[(size_t) ci * och + co]);
+          rw = f_bits (r);
+        }
+        ((aconv_u32 *) mid)[oi] = rw;
+        break;
+      }
+      default: {
+        uint64_t rw;
+        if (!p.mix) {
+          rw = x8[co];
+        } else {
+          double r = 0.0;
+          for (int ci = 0; ci < p.in_ch; ci++)
+            if ((use >> ci) & 1u)
+              r += bits_d (x8[ci]) * bits_f (mw[(size_t) ci * och + co]);
+          rw = d_bits (r);
+        }
+        ((aconv_u64 *) mid)[oi] = rw;
+        break;
+      }
+    }
+  }
+}
+
+// head[] of the rows of a wide second kernel (host): row y writes plane y alone
+inline void aconv_planes_heads_wide (AConvPlanesWide *pl, int planes, int bytes, bool grouped)
+{
+  for (int y = 0; y < GSTAMD_AUDIO_MAX_CHANNELS_WIDE; y++) {
+    const AConvSplit s = y < planes ? aconv_split (pl->p[y], bytes, pl->frames, grouped) : AConvSplit { 0, 0, 0 };
+    pl->head[y] = s.groups ? (uint8_t) s.head : 4;
+  }
+  pl->realign = 0;
+}
+
+inline size_t aconv_planes_lanes_wide (const AConvPlanesWide &pl, int rows)
+{
+  size_t m = 0;
+  for (int y = 0; y < rows; y++) {
+    const size_t l = aconv_split_lanes (aconv_plane_split_of (pl, y));
+    m = l > m ? l : m;
+  }
+  return m;
+}
 
 // ---- the endian plan (converter_endian): every sample's bytes reversed, nothing else.  K is the little-endian container of the width;
 // reading it as LE and writing it as BE is the swap in either direction.  in == out is fine: a lane reads its bytes before it writes them.

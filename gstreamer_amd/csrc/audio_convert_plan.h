@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/gstamd_video.h"
 #include "audio_convert_device.h"
@@ -46,11 +47,12 @@ enum APos : int {
   APOS_RC = 8, APOS_LFE2 = 9, APOS_SL = 10, APOS_SR = 11
 };
 
-typedef float AMixMatrix[GSTAMD_AUDIO_MAX_CHANNELS][GSTAMD_AUDIO_MAX_CHANNELS];
+// The matrices are flat [in][out] arrays with a row stride `ms`: 8 inside an AConvPlan, the output channel count in a wide plan.
 
 // fill_compatible (:163-253): mono <-> stereo pairs of the front, the centre pair and the rear
-static void amix_fill_compatible (AMixMatrix m, int in_ch, const int *ip, int out_ch, const int *op)
+static void amix_fill_compatible (float *m, int ms, int in_ch, const int *ip, int out_ch, const int *op)
 {
+  auto M = [&](int i, int j) -> float & { return m[i * ms + j]; };
   static const int conv[3][3] = { {APOS_FL, APOS_FR, APOS_MONO}, {APOS_FLOC, APOS_FROC, APOS_FC}, {APOS_RL, APOS_RR, APOS_RC} };
   for (int c = 0; c < 3; c++) {
     int a0 = -1, a1 = -1, a2 = -1, b0 = -1, b1 = -1, b2 = -1;
@@ -65,19 +67,19 @@ static void amix_fill_compatible (AMixMatrix m, int in_ch, const int *ip, int ou
       else if (op[n] == conv[c][2]) b2 = n;
     }
     /* left -> centre, right -> centre */
-    if (a0 != -1 && a2 == -1 && b0 == -1 && b2 != -1) m[a0][b2] = 1.0f;
-    else if (a0 != -1 && a2 != -1 && b0 == -1 && b2 != -1) m[a0][b2] = 0.5f;
-    else if (a0 != -1 && a2 == -1 && b0 != -1 && b2 != -1) m[a0][b2] = 1.0f;
-    if (a1 != -1 && a2 == -1 && b1 == -1 && b2 != -1) m[a1][b2] = 1.0f;
-    else if (a1 != -1 && a2 != -1 && b1 == -1 && b2 != -1) m[a1][b2] = 0.5f;
-    else if (a1 != -1 && a2 == -1 && b1 != -1 && b2 != -1) m[a1][b2] = 1.0f;
+    if (a0 != -1 && a2 == -1 && b0 == -1 && b2 != -1) M (a0, b2) = 1.0f;
+    else if (a0 != -1 && a2 != -1 && b0 == -1 && b2 != -1) M (a0, b2) = 0.5f;
+    else if (a0 != -1 && a2 == -1 && b0 != -1 && b2 != -1) M (a0, b2) = 1.0f;
+    if (a1 != -1 && a2 == -1 && b1 == -1 && b2 != -1) M (a1, b2) = 1.0f;
+    else if (a1 != -1 && a2 != -1 && b1 == -1 && b2 != -1) M (a1, b2) = 0.5f;
+    else if (a1 != -1 && a2 == -1 && b1 != -1 && b2 != -1) M (a1, b2) = 1.0f;
     /* centre -> left, centre -> right */
-    if (a2 != -1 && a0 == -1 && b2 == -1 && b0 != -1) m[a2][b0] = 1.0f;
-    else if (a2 != -1 && a0 != -1 && b2 == -1 && b0 != -1) m[a2][b0] = 0.5f;
-    else if (a2 != -1 && a0 == -1 && b2 != -1 && b0 != -1) m[a2][b0] = 1.0f;
-    if (a2 != -1 && a1 == -1 && b2 == -1 && b1 != -1) m[a2][b1] = 1.0f;
-    else if (a2 != -1 && a1 != -1 && b2 == -1 && b1 != -1) m[a2][b1] = 0.5f;
-    else if (a2 != -1 && a1 == -1 && b2 != -1 && b1 != -1) m[a2][b1] = 1.0f;
+    if (a2 != -1 && a0 == -1 && b2 == -1 && b0 != -1) M (a2, b0) = 1.0f;
+    else if (a2 != -1 && a0 != -1 && b2 == -1 && b0 != -1) M (a2, b0) = 0.5f;
+    else if (a2 != -1 && a0 == -1 && b2 != -1 && b0 != -1) M (a2, b0) = 1.0f;
+    if (a2 != -1 && a1 == -1 && b2 == -1 && b1 != -1) M (a2, b1) = 1.0f;
+    else if (a2 != -1 && a1 != -1 && b2 == -1 && b1 != -1) M (a2, b1) = 0.5f;
+    else if (a2 != -1 && a1 == -1 && b2 != -1 && b1 != -1) M (a2, b1) = 1.0f;
   }
 }
 
@@ -107,20 +109,21 @@ static void amix_detect (int ch, const int *pos, AMixGroups &g)
 }
 
 // fill_one_other (:329-378); `ratio` is a gfloat there and 0.5 * ratio is rounded to float on the store
-static void amix_one_other (AMixMatrix m, const int *from, const int *to, float ratio)
+static void amix_one_other (float *m, int ms, const int *from, const int *to, float ratio)
 {
   const float half = (float) (0.5 * (double) ratio);
-  if (from[1] != -1 && to[1] != -1) m[from[1]][to[1]] = ratio;
-  if (from[0] != -1 && to[0] != -1) m[from[0]][to[0]] = ratio;
-  if (from[2] != -1 && to[2] != -1) m[from[2]][to[2]] = ratio;
-  if (from[0] != -1 && to[1] != -1) m[from[0]][to[1]] = from[1] != -1 ? half : ratio;
-  if (from[2] != -1 && to[1] != -1) m[from[2]][to[1]] = from[1] != -1 ? half : ratio;
-  if (from[1] != -1 && to[0] != -1) m[from[1]][to[0]] = from[0] != -1 ? half : ratio;
-  if (from[1] != -1 && to[2] != -1) m[from[1]][to[2]] = from[2] != -1 ? half : ratio;
+  auto M = [&](int i, int j) -> float & { return m[i * ms + j]; };
+  if (from[1] != -1 && to[1] != -1) M (from[1], to[1]) = ratio;
+  if (from[0] != -1 && to[0] != -1) M (from[0], to[0]) = ratio;
+  if (from[2] != -1 && to[2] != -1) M (from[2], to[2]) = ratio;
+  if (from[0] != -1 && to[1] != -1) M (from[0], to[1]) = from[1] != -1 ? half : ratio;
+  if (from[2] != -1 && to[1] != -1) M (from[2], to[1]) = from[1] != -1 ? half : ratio;
+  if (from[1] != -1 && to[0] != -1) M (from[1], to[0]) = from[0] != -1 ? half : ratio;
+  if (from[1] != -1 && to[2] != -1) M (from[1], to[2]) = from[2] != -1 ? half : ratio;
 }
 
 // fill_others (:398-590): a family one side lacks goes to / comes from the nearest family the other side has
-static void amix_fill_others (AMixMatrix m, int in_ch, const int *ip, int out_ch, const int *op)
+static void amix_fill_others (float *m, int ms, int in_ch, const int *ip, int out_ch, const int *op)
 {
   AMixGroups i, o;
   amix_detect (in_ch, ip, i);
@@ -128,7 +131,7 @@ static void amix_fill_others (AMixMatrix m, int in_ch, const int *ip, int out_ch
   const double R2 = 1.0 / sqrt (2.0), R8 = 1.0 / sqrt (8.0);
   const double CENTER_FRONT = R2, CENTER_SIDE = 0.5, CENTER_REAR = R8, FRONT_SIDE = R2, FRONT_REAR = 0.5, SIDE_REAR = R2;
   const double CENTER_BASS = R2, FRONT_BASS = 1.0, SIDE_BASS = R2, REAR_BASS = R2;
-  auto go = [&](const int *from, const int *to, double ratio) { amix_one_other (m, from, to, (float) ratio); };
+  auto go = [&](const int *from, const int *to, double ratio) { amix_one_other (m, ms, from, to, (float) ratio); };
   /* centre <-> front / side / rear */
   if (!i.has_c && i.has_f && o.has_c) go (i.f, o.c, CENTER_FRONT);
   else if (!i.has_c && !i.has_f && i.has_s && o.has_c) go (i.s, o.c, CENTER_SIDE);
@@ -176,13 +179,14 @@ static void amix_fill_others (AMixMatrix m, int in_ch, const int *ip, int out_ch
 }
 
 // fill_normalize (:596-626): float sums of |m| per output channel, every entry divided by the largest
-static void amix_normalize (AMixMatrix m, int in_ch, int out_ch)
+static void amix_normalize (float *m, int ms, int in_ch, int out_ch)
 {
+  auto M = [&](int i, int j) -> float & { return m[i * ms + j]; };
   float top = 0;
   for (int j = 0; j < out_ch; j++) {
     float sum = 0.0f;
     for (int i = 0; i < in_ch; i++)
-      sum = (float) ((double) sum + fabs ((double) m[i][j]));
+      sum = (float) ((double) sum + fabs ((double) M (i, j)));
     if (sum > top)
       top = sum;
   }
@@ -190,21 +194,21 @@ static void amix_normalize (AMixMatrix m, int in_ch, int out_ch)
     return;
   for (int j = 0; j < out_ch; j++)
     for (int i = 0; i < in_ch; i++)
-      m[i][j] /= top;
+      M (i, j) /= top;
 }
 
-static void default_mix_matrix (const GstAmdAudioInfo &in, const GstAmdAudioInfo &out, AMixMatrix m)
+// m: in_ch rows of ms floats
+static void default_mix_matrix (int in_ch, const int *ip, bool in_unpositioned, int out_ch, const int *op, float *m, int ms)
 {
-  memset (m, 0, sizeof (AMixMatrix));
-  const int *ip = in.position, *op = out.position;
-  const int in_ch = in.channels, out_ch = out.channels;
+  memset (m, 0, sizeof (float) * (size_t) in_ch * (size_t) ms);
+  auto M = [&](int i, int j) -> float & { return m[i * ms + j]; };
   /* fill_special (:628-656) */
   if (in_ch == 2 && out_ch == 1 && ((ip[0] == APOS_FL && ip[1] == APOS_FR) || (ip[0] == APOS_FR && ip[1] == APOS_FL)) && op[0] == APOS_MONO) {
-    m[0][0] = m[1][0] = 0.5f;
+    M (0, 0) = M (1, 0) = 0.5f;
     return;
   }
   if (in_ch == 1 && out_ch == 2 && ((op[0] == APOS_FL && op[1] == APOS_FR) || (op[0] == APOS_FR && op[1] == APOS_FL)) && ip[0] == APOS_MONO) {
-    m[0][0] = m[0][1] = 1.0f;
+    M (0, 0) = M (0, 1) = 1.0f;
     return;
   }
   /* virtual inputs (:684-729): all-mono inputs count as one mono channel, alternating left / right ones as one stereo pair */
@@ -221,31 +225,37 @@ static void default_mix_matrix (const GstAmdAudioInfo &in, const GstAmdAudioInfo
   /* fill_identical (:130-155) */
   for (int co = 0; co < out_ch; co++)
     for (int ci = 0; ci < in_size; ci++) {
-      if (in.unpositioned)
-        m[ci][co] = ci == co ? 1.0f : 0.0f;
+      if (in_unpositioned)
+        M (ci, co) = ci == co ? 1.0f : 0.0f;
       else if (ip[ci] == op[co])
-        m[ci][co] = 1.0f;
+        M (ci, co) = 1.0f;
     }
-  if (!in.unpositioned) {
-    amix_fill_compatible (m, in_size, ip, out_ch, op);
-    amix_fill_others (m, in_size, ip, out_ch, op);
-    amix_normalize (m, in_size, out_ch);
+  if (!in_unpositioned) {
+    amix_fill_compatible (m, ms, in_size, ip, out_ch, op);
+    amix_fill_others (m, ms, in_size, ip, out_ch, op);
+    amix_normalize (m, ms, in_size, out_ch);
   }
   if (virt == 1) {
     for (int o = 0; o < out_ch; o++)
-      m[0][o] /= (float) in_ch;
+      M (0, o) /= (float) in_ch;
     for (int i = 1; i < in_ch; i++)
-      memcpy (m[i], m[0], sizeof (float) * (size_t) out_ch);
+      memcpy (&M (i, 0), &M (0, 0), sizeof (float) * (size_t) out_ch);
   } else if (virt == 2) {
     const int right = in_ch >> 1, left = right + (in_ch % 2);
     for (int o = 0; o < out_ch; o++) {
-      m[0][o] /= (float) left;
-      m[1][o] /= (float) right;
+      M (0, o) /= (float) left;
+      M (1, o) /= (float) right;
     }
     for (int i = 2; i < in_ch; i++)
-      memcpy (m[i], m[i % 2], sizeof (float) * (size_t) out_ch);
+      memcpy (&M (i, 0), &M (i % 2, 0), sizeof (float) * (size_t) out_ch);
   }
 }
+
+// one side of a conversion as the chain decisions see it: a GstAmdAudioInfo or a GstAmdAudioInfoWide
+struct AConvSide {
+  int format, rate, channels, info_layout, unpositioned;
+  const int *position;
+};
 
 // The whole plan.  *resample: a resampler (on p->mid_in, out->channels) sits between the two kernels; *passthrough: the bytes
 // themselves; plan->endian_swap: the bytes of every sample reversed.  Returns GSTAMD_OK or an error code with *err set.
@@ -253,54 +263,56 @@ static void default_mix_matrix (const GstAmdAudioInfo &in, const GstAmdAudioInfo
 //   - the passthrough and the endian shortcut need equal layouts; where the layouts differ the mix stage runs even with a passthrough
 //     matrix (the mixer is what changes the layout), on the intermediate format the rules below give anyway;
 //   - the quantizer of a non-interleaved output walks plane after plane as one channel: q_stride 1.
-inline int aconv_make_plan_layouts (int flags, const GstAmdAudioInfo *in, int in_layout, const GstAmdAudioInfo *out, int out_layout,
-    const GstAmdAudioConverterConfig &cfg, AConvPlan *plan, bool *resample, bool *passthrough, std::string *err)
+// The chain does not depend on the channel count: this is the plan of both constructors.  max_ch: 8 or 64.  user: the mix-matrix option,
+// [out][in] with row stride us, or NULL.  m / mi: the matrices, [in][out] with row stride ms; use[out]: the channels the mixer sums.
+// plan->m / mi / use are not touched here (aconv_make_plan_layouts points m / mi at them).
+inline int aconv_plan_chain (int flags, const AConvSide &in, int in_layout, const AConvSide &out, int out_layout, const GstAmdAudioConverterConfig &cfg, int max_ch,
+    const float *user, int us, AConvPlan *plan, float *m, int *mi, int ms, uint64_t *use, bool *resample, bool *passthrough, std::string *err)
 {
   if (in_layout < 0 || in_layout > 1 || out_layout < 0 || out_layout > 1) {
     *err = "layout is 0 (interleaved) or 1 (non-interleaved)";
     return GSTAMD_ERR_INVALID;
   }
-  const AFmtInfo fi = afmt_info (in->format), fo = afmt_info (out->format);
+  const AFmtInfo fi = afmt_info (in.format), fo = afmt_info (out.format);
   if (!fi.known || !fo.known) {
     *err = "not a raw sample format (GstAudioFormat 2 .. 31: S8 / U8, S16 / S24_32 / S32 / S24 / S20 / S18 signed and unsigned, F32 / F64, either byte order)";
     return GSTAMD_ERR_UNSUPPORTED;
   }
-  if (in->channels < 1 || out->channels < 1 || in->channels > GSTAMD_AUDIO_MAX_CHANNELS || out->channels > GSTAMD_AUDIO_MAX_CHANNELS) {
-    *err = "1 .. 8 channels";
-    return GSTAMD_ERR_UNSUPPORTED;
+  if (in.channels < 1 || out.channels < 1 || in.channels > max_ch || out.channels > max_ch) {
+    *err = max_ch == GSTAMD_AUDIO_MAX_CHANNELS ? "1 .. 8 channels" : "1 .. 64 channels";
+    return max_ch == GSTAMD_AUDIO_MAX_CHANNELS ? GSTAMD_ERR_UNSUPPORTED : GSTAMD_ERR_INVALID;     /* 64 is the reference's limit too */
   }
-  if (in->layout != 0 || out->layout != 0) {
+  if (in.info_layout != 0 || out.info_layout != 0) {
     *err = "GstAmdAudioInfo.layout is 0: non-interleaved layouts are the layout arguments of gstamd_audio_converter_new_layouts";
     return GSTAMD_ERR_UNSUPPORTED;
   }
-  if (in->rate <= 0 || out->rate <= 0) {
+  if (in.rate <= 0 || out.rate <= 0) {
     *err = "bad rate";
     return GSTAMD_ERR_INVALID;
   }
   /* gst_audio_converter_new :1370-1378 */
-  if (!cfg.has_mix_matrix && in->channels != out->channels && (in->unpositioned || out->unpositioned)) {
+  if (!user && in.channels != out.channels && (in.unpositioned || out.unpositioned)) {
     *err = "unpositioned channels with different channel counts and no mix-matrix";
     return GSTAMD_ERR_INVALID;
   }
   AConvPlan &p = *plan;
-  memset (&p, 0, sizeof (p));
-  p.in_fmt = in->format;
-  p.out_fmt = out->format;
-  p.in_ch = in->channels;
-  p.out_ch = out->channels;
-  p.q_stride = out_layout ? 1 : out->channels;
+  p.in_fmt = in.format;
+  p.out_fmt = out.format;
+  p.in_ch = in.channels;
+  p.out_ch = out.channels;
+  p.q_stride = out_layout ? 1 : out.channels;
   {
-    const AFmtDesc di = afmt_desc (in->format), dout = afmt_desc (out->format);
-    p.in_kind = afmt_kind (in->format);
-    p.out_kind = afmt_kind (out->format);
+    const AFmtDesc di = afmt_desc (in.format), dout = afmt_desc (out.format);
+    p.in_kind = afmt_kind (in.format);
+    p.out_kind = afmt_kind (out.format);
     p.in_shift = di.integer ? 32 - di.depth : 0;
     p.in_sx = di.integer && di.usgn ? 0x80000000u : 0u;
     p.out_shift = dout.integer ? 32 - dout.depth : 0;
     p.out_usgn = dout.integer && dout.usgn ? 1 : 0;
   }
   /* chain_unpack :708-740 */
-  const bool same_format = in->format == out->format;
-  int cur = (same_format && afmt_is_intermediate (in->format)) ? afmt_mid (in->format) : (fi.integer ? AMID_S32 : AMID_F64);
+  const bool same_format = in.format == out.format;
+  int cur = (same_format && afmt_is_intermediate (in.format)) ? afmt_mid (in.format) : (fi.integer ? AMID_S32 : AMID_F64);
   /* chain_convert_in :742-762 */
   if (fi.integer && !fo.integer) {
     p.convert_in = 1;
@@ -308,41 +320,41 @@ inline int aconv_make_plan_layouts (int flags, const GstAmdAudioInfo *in, int in
   }
   p.mid_in = cur;
   /* chain_mix :849-902 */
-  if (cfg.has_mix_matrix) {
-    for (int ci = 0; ci < in->channels; ci++)
-      for (int co = 0; co < out->channels; co++)
-        p.m[ci][co] = cfg.mix_matrix[co][ci];           /* mix_matrix_from_g_value: the option is [out][in] */
+  if (user) {
+    for (int ci = 0; ci < in.channels; ci++)
+      for (int co = 0; co < out.channels; co++)
+        m[ci * ms + co] = user[co * us + ci];           /* mix_matrix_from_g_value: the option is [out][in] */
   } else {
-    default_mix_matrix (*in, *out, p.m);
+    default_mix_matrix (in.channels, in.position, in.unpositioned != 0, out.channels, out.position, m, ms);
   }
   /* gst_audio_channel_mixer_build_sparse_matrix (:1063-1122): with fewer than half of the coefficients above 1e-6 the mixer walks a
      list of those only - the others are not summed at all (which matters for float samples: inf * 0) */
   {
     int pairs = 0;
-    for (int ci = 0; ci < in->channels; ci++)
-      for (int co = 0; co < out->channels; co++)
-        if (fabsf (p.m[ci][co]) > 1e-6f)
+    for (int ci = 0; ci < in.channels; ci++)
+      for (int co = 0; co < out.channels; co++)
+        if (fabsf (m[ci * ms + co]) > 1e-6f)
           pairs++;
-    p.sparse = (double) pairs / (double) (in->channels * out->channels) < 0.5 ? 1 : 0;
-    for (int co = 0; co < out->channels; co++) {
-      p.use[co] = 0;
-      for (int ci = 0; ci < in->channels; ci++)
-        if (!p.sparse || fabsf (p.m[ci][co]) > 1e-6f)
-          p.use[co] |= 1u << ci;
+    p.sparse = (double) pairs / (double) (in.channels * out.channels) < 0.5 ? 1 : 0;
+    for (int co = 0; co < out.channels; co++) {
+      use[co] = 0;
+      for (int ci = 0; ci < in.channels; ci++)
+        if (!p.sparse || fabsf (m[ci * ms + co]) > 1e-6f)
+          use[co] |= (uint64_t) 1 << ci;
     }
   }
-  for (int ci = 0; ci < in->channels; ci++)
-    for (int co = 0; co < out->channels; co++) {
-      const float tmp = p.m[ci][co] * (float) (1 << 10);        /* gst_audio_channel_mixer_setup_matrix_int */
-      p.mi[ci][co] = (int) tmp;
+  for (int ci = 0; ci < in.channels; ci++)
+    for (int co = 0; co < out.channels; co++) {
+      const float tmp = m[ci * ms + co] * (float) (1 << 10);    /* gst_audio_channel_mixer_setup_matrix_int */
+      mi[ci * ms + co] = (int) tmp;
     }
-  bool mix_passthrough = in->channels == out->channels && in_layout == out_layout;
-  for (int i = 0; i < in->channels && mix_passthrough; i++)
-    for (int j = 0; j < out->channels && mix_passthrough; j++)
-      mix_passthrough = p.m[i][j] == (i == j ? 1.0f : 0.0f);
+  bool mix_passthrough = in.channels == out.channels && in_layout == out_layout;
+  for (int i = 0; i < in.channels && mix_passthrough; i++)
+    for (int j = 0; j < out.channels && mix_passthrough; j++)
+      mix_passthrough = m[i * ms + j] == (i == j ? 1.0f : 0.0f);
   p.mix = mix_passthrough ? 0 : 1;
   /* chain_resample :904-943 */
-  *resample = in->rate != out->rate || (flags & 2) != 0;
+  *resample = in.rate != out.rate || (flags & 2) != 0;
   /* chain_convert_out :945-966 */
   if (!fi.integer && fo.integer) {
     p.convert_out = 1;
@@ -357,7 +369,7 @@ inline int aconv_make_plan_layouts (int flags, const GstAmdAudioInfo *in, int in
     if ((unsigned) fo.depth > cfg.dither_threshold || (in_int && fo.depth >= in_depth)) {
       dither = GSTAMD_AUDIO_DITHER_NONE;
       ns = 0;
-    } else if (ns > 1 && out->rate < 32000) {
+    } else if (ns > 1 && out.rate < 32000) {
       ns = 1;
     }
     if (fo.integer && fo.depth < 32 && cur == AMID_S32) {
@@ -382,11 +394,25 @@ inline int aconv_make_plan_layouts (int flags, const GstAmdAudioInfo *in, int in
   *passthrough = mix_passthrough && same_format && !*resample;
   /* the same, with formats that differ in byte order only: converter_endian, a byte swap of the samples as they are - no unpack, no
      quantize (so no dither), and floats are not looked at (denormals and NaN payloads pass) */
-  if (mix_passthrough && !*resample && afmt_endian_pair (in->format, out->format)) {
-    p.endian_swap = afmt_bytes (in->format);
+  if (mix_passthrough && !*resample && afmt_endian_pair (in.format, out.format)) {
+    p.endian_swap = afmt_bytes (in.format);
     p.quant_shift = p.dither = p.ns = p.n_coeffs = 0;           /* this chain has no quantizer */
   }
   return GSTAMD_OK;
+}
+
+inline int aconv_make_plan_layouts (int flags, const GstAmdAudioInfo *in, int in_layout, const GstAmdAudioInfo *out, int out_layout,
+    const GstAmdAudioConverterConfig &cfg, AConvPlan *plan, bool *resample, bool *passthrough, std::string *err)
+{
+  const AConvSide si = { in->format, in->rate, in->channels, in->layout, in->unpositioned, in->position };
+  const AConvSide so = { out->format, out->rate, out->channels, out->layout, out->unpositioned, out->position };
+  uint64_t use[GSTAMD_AUDIO_MAX_CHANNELS] = { 0 };
+  memset (plan, 0, sizeof (*plan));
+  const int r = aconv_plan_chain (flags, si, in_layout, so, out_layout, cfg, GSTAMD_AUDIO_MAX_CHANNELS, cfg.has_mix_matrix ? &cfg.mix_matrix[0][0] : nullptr,
+      GSTAMD_AUDIO_MAX_CHANNELS, plan, &plan->m[0][0], &plan->mi[0][0], GSTAMD_AUDIO_MAX_CHANNELS, use, resample, passthrough, err);
+  for (int co = 0; co < GSTAMD_AUDIO_MAX_CHANNELS; co++)
+    plan->use[co] = (uint32_t) use[co];
+  return r;
 }
 
 // gst_audio_converter_new with two interleaved infos
@@ -396,5 +422,34 @@ inline int aconv_make_plan (int flags, const GstAmdAudioInfo *in, const GstAmdAu
   return aconv_make_plan_layouts (flags, in, 0, out, 0, cfg, plan, resample, passthrough, err);
 }
 
-}  // namespace gstamd
+// ---- the wide plan (1 .. 64 channels): the scalar fields of an AConvPlan - whose own m / mi / use stay zero -, and the
+// matrices beside it as the mixing kernel reads them from device memory: [in][out] with row stride out_ch, a 64-bit use[out]
+struct AConvWidePlan {
+  AConvPlan s;
+  std::vector<float> m;
+  std::vector<int32_t> mi;
+  std::vector<uint64_t> use;
+};
 
+// mix_matrix: NULL, or out->channels rows of in->channels floats
+inline int aconv_make_plan_wide (int flags, const GstAmdAudioInfoWide *in, int in_layout, const GstAmdAudioInfoWide *out, int out_layout,
+    const GstAmdAudioConverterConfig &cfg, const float *mix_matrix, AConvWidePlan *plan, bool *resample, bool *passthrough, std::string *err)
+{
+  if (cfg.has_mix_matrix) {
+    *err = "config->has_mix_matrix is 0 here: the matrix is the mix_matrix argument of gstamd_audio_converter_new_wide";
+    return GSTAMD_ERR_INVALID;
+  }
+  const AConvSide si = { in->format, in->rate, in->channels, in->layout, in->unpositioned, in->position };
+  const AConvSide so = { out->format, out->rate, out->channels, out->layout, out->unpositioned, out->position };
+  memset (&plan->s, 0, sizeof (plan->s));
+  const bool counts = in->channels >= 1 && out->channels >= 1 && in->channels <= GSTAMD_AUDIO_MAX_CHANNELS_WIDE && out->channels <= GSTAMD_AUDIO_MAX_CHANNELS_WIDE;
+  const size_t n = counts ? (size_t) in->channels * (size_t) out->channels : 1;
+  plan->m.assign (n, 0.0f);
+  plan->mi.assign (n, 0);
+  plan->use.assign (GSTAMD_AUDIO_MAX_CHANNELS_WIDE, 0);
+  static_assert (sizeof (int) == sizeof (int32_t), "mi");
+  return aconv_plan_chain (flags, si, in_layout, so, out_layout, cfg, GSTAMD_AUDIO_MAX_CHANNELS_WIDE, mix_matrix, in->channels, &plan->s, plan->m.data (),
+      (int *) plan->mi.data (), out->channels, plan->use.data (), resample, passthrough, err);
+}
+
+}  // namespace gstamd

@@ -136,6 +136,7 @@ enum {
 /* GstAudioDitherMethod / GstAudioNoiseShapingMethod (audio-quantize.h:45-72) */
 enum { GSTAMD_AUDIO_DITHER_NONE = 0, GSTAMD_AUDIO_DITHER_RPDF = 1, GSTAMD_AUDIO_DITHER_TPDF = 2, GSTAMD_AUDIO_DITHER_TPDF_HF = 3 };
 #define GSTAMD_AUDIO_MAX_CHANNELS 8
+#define GSTAMD_AUDIO_MAX_CHANNELS_WIDE 64       /* GstAudioInfo's own limit: gstamd_audio_converter_new_wide */
 enum { GSTAMD_AUDIO_LAYOUT_INTERLEAVED = 0, GSTAMD_AUDIO_LAYOUT_NON_INTERLEAVED = 1 };  /* GstAudioLayout */
 
 typedef struct GstAmdAudioInfo {
@@ -145,6 +146,15 @@ typedef struct GstAmdAudioInfo {
   int32_t unpositioned;         /* GST_AUDIO_FLAG_UNPOSITIONED */
   int32_t position[GSTAMD_AUDIO_MAX_CHANNELS];  /* GstAudioChannelPosition values (audio-channels.h:101-133): NONE -3, MONO -2, FRONT_LEFT 0, FRONT_RIGHT 1, FRONT_CENTER 2, LFE1 3, REAR_LEFT 4, ... */
 } GstAmdAudioInfo;
+
+/* GstAmdAudioInfo with the 64 positions a GstAudioInfo holds (gstamd_audio_converter_new_wide) */
+typedef struct GstAmdAudioInfoWide {
+  int32_t format;
+  int32_t rate, channels;
+  int32_t layout;               /* 0, as in GstAmdAudioInfo */
+  int32_t unpositioned;
+  int32_t position[GSTAMD_AUDIO_MAX_CHANNELS_WIDE];
+} GstAmdAudioInfoWide;
 
 typedef struct GstAmdAudioConverterConfig {
   int32_t dither_method;        /* GstAudioConverter.dither-method (library default: none) */
@@ -171,6 +181,13 @@ GstAmdAudioConverter *gstamd_audio_converter_new (int flags, const GstAmdAudioIn
  * non-interleaved output dithers and shapes plane after plane as ONE channel, as gst_audio_quantize_samples does. */
 GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAmdAudioInfo *in_info, int in_layout,
     const GstAmdAudioInfo *out_info, int out_layout, const GstAmdAudioConverterConfig *config, int *status);
+/* gstamd_audio_converter_new_layouts for 1 .. 64 channels on each side.  mix_matrix: NULL for the default matrix, else
+ * out_info->channels rows of in_info->channels floats, [out][in] as the GstAudioConverter.mix-matrix option; config->has_mix_matrix must be 0
+ * (its [8][8] array cannot hold the matrix).  The converter keeps its matrix in device memory and mixes a tile of frames through LDS; it
+ * does so at 8 channels or fewer too, where it gives the bytes of the converter gstamd_audio_converter_new_layouts makes.  Every other entry
+ * point works on it; gstamd_audio_converter_samples_planes takes up to 64 plane pointers. */
+GstAmdAudioConverter *gstamd_audio_converter_new_wide (int flags, const GstAmdAudioInfoWide *in_info, int in_layout,
+    const GstAmdAudioInfoWide *out_info, int out_layout, const GstAmdAudioConverterConfig *config, const float *mix_matrix, int *status);
 void gstamd_audio_converter_free (GstAmdAudioConverter *convert);
 void gstamd_audio_converter_reset (GstAmdAudioConverter *convert);
 size_t gstamd_audio_converter_get_out_frames (GstAmdAudioConverter *convert, size_t in_frames);

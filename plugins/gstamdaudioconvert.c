@@ -8,7 +8,8 @@
  * (:309-337).  Samples are staged to HBM per buffer like the audioresample element's.  Both layouts on both pads: a non-interleaved
  * side is staged as [channels][frames] (the planes of an input buffer are where its GstAudioMeta says, those of an output buffer back
  * to back with a GstAudioMeta added, as in gstamdaudioresample.c) and converted by gstamd_audio_converter_new_layouts; fixation
- * prefers the input's layout.
+ * prefers the input's layout.  1 .. 64 channels on each side: with more than 8 on either one the converter is made by
+ * gstamd_audio_converter_new_wide, otherwise by gstamd_audio_converter_new_layouts as before.
  * Not implemented: input-channels-reorder / -mode, the depth / sign scoring of fixate_format (:1237-1340;
  * this element prefers the input's format, then the widest one the peer offers of the same kind).
  */
@@ -28,7 +29,7 @@ GST_DEBUG_CATEGORY_STATIC (amd_ac_debug);
 #define AMD_AC_FORMATS "{ F64LE, F32LE, S32LE, S24_32LE, S24LE, S16LE, S8, U8, U32LE, U24_32LE, U24LE, S20LE, U20LE, S18LE, U18LE, U16LE, " \
     "F64BE, F32BE, S32BE, U32BE, S24_32BE, U24_32BE, S24BE, U24BE, S20BE, U20BE, S18BE, U18BE, S16BE, U16BE }"
 #define AMD_AC_CAPS "audio/x-raw, format = (string) " AMD_AC_FORMATS ", rate = (int) [ 1, MAX ], " \
-    "channels = (int) [ 1, 8 ], layout = (string) { interleaved, non-interleaved }"
+    "channels = (int) [ 1, 64 ], layout = (string) { interleaved, non-interleaved }"
 
 static GstStaticPadTemplate ac_sink = GST_STATIC_PAD_TEMPLATE ("sink", GST_PAD_SINK, GST_PAD_ALWAYS, GST_STATIC_CAPS (AMD_AC_CAPS));
 static GstStaticPadTemplate ac_src = GST_STATIC_PAD_TEMPLATE ("src", GST_PAD_SRC, GST_PAD_ALWAYS, GST_STATIC_CAPS (AMD_AC_CAPS));
@@ -268,7 +269,7 @@ amd_ac_fixate_caps (GstBaseTransform * t, GstPadDirection direction, GstCaps * c
 }
 
 static gboolean
-amd_ac_info (const GstAudioInfo * i, GstAmdAudioInfo * a)
+amd_ac_info (const GstAudioInfo * i, GstAmdAudioInfoWide * a)
 {
   gint c;
   memset (a, 0, sizeof (*a));
@@ -276,15 +277,29 @@ amd_ac_info (const GstAudioInfo * i, GstAmdAudioInfo * a)
   if (GST_AUDIO_INFO_FORMAT (i) < GST_AUDIO_FORMAT_S8 || GST_AUDIO_INFO_FORMAT (i) > GST_AUDIO_FORMAT_F64BE)
     return FALSE;
   a->format = (int32_t) GST_AUDIO_INFO_FORMAT (i);
-  if (GST_AUDIO_INFO_CHANNELS (i) > GSTAMD_AUDIO_MAX_CHANNELS)
+  if (GST_AUDIO_INFO_CHANNELS (i) < 1 || GST_AUDIO_INFO_CHANNELS (i) > GSTAMD_AUDIO_MAX_CHANNELS_WIDE)
     return FALSE;
   a->rate = GST_AUDIO_INFO_RATE (i);
   a->channels = GST_AUDIO_INFO_CHANNELS (i);
-  a->layout = 0;                /* the layouts go to gstamd_audio_converter_new_layouts beside the infos (amd_ac_layout) */
+  a->layout = 0;                /* the layouts go to the constructor beside the infos (amd_ac_layout) */
   a->unpositioned = GST_AUDIO_INFO_IS_UNPOSITIONED (i) ? 1 : 0;
   for (c = 0; c < a->channels; c++)
     a->position[c] = (int32_t) i->position[c];          /* GstAudioChannelPosition values as they are */
   return TRUE;
+}
+
+/* the same info for gstamd_audio_converter_new_layouts (at most 8 channels) */
+static void
+amd_ac_info_narrow (const GstAmdAudioInfoWide * w, GstAmdAudioInfo * a)
+{
+  gint c;
+  memset (a, 0, sizeof (*a));
+  a->format = w->format;
+  a->rate = w->rate;
+  a->channels = w->channels;
+  a->unpositioned = w->unpositioned;
+  for (c = 0; c < w->channels && c < GSTAMD_AUDIO_MAX_CHANNELS; c++)
+    a->position[c] = w->position[c];
 }
 
 static int
@@ -299,8 +314,10 @@ static gboolean
 amd_ac_ensure_converter (GstAmdAudioConvert * s)
 {
   GstBaseTransform *t = GST_BASE_TRANSFORM (s);
-  GstAmdAudioInfo ai, ao;
+  GstAmdAudioInfoWide ai, ao;
   GstAmdAudioConverterConfig cfg;
+  gfloat *matrix = NULL;        /* [out][in], rows of ai.channels */
+  gboolean wide;
   int status = 0;
 
   GST_OBJECT_LOCK (s);
@@ -326,28 +343,45 @@ amd_ac_ensure_converter (GstAmdAudioConvert * s)
   if (s->mix_matrix_is_set) {
     const guint rows = gst_value_array_get_size (&s->mix_matrix);
     guint r, c;
-    cfg.has_mix_matrix = 1;
+    matrix = g_new0 (gfloat, (gsize) ai.channels * (gsize) ao.channels);
     if (rows == 0) {
       /* an empty matrix: gst_audio_channel_mixer_new_with_matrix makes a (truncated) identity (audio-channel-mixer.c:1160-1172) */
-      for (r = 0; r < GSTAMD_AUDIO_MAX_CHANNELS; r++)
-        cfg.mix_matrix[r][r] = 1.0f;
+      for (r = 0; r < (guint) MIN (ai.channels, ao.channels); r++)
+        matrix[r * (guint) ai.channels + r] = 1.0f;
     } else {
       const guint cols = gst_value_array_get_size (gst_value_array_get_value (&s->mix_matrix, 0));
       if (rows != (guint) ao.channels || cols != (guint) ai.channels) {
         GST_OBJECT_UNLOCK (s);
+        g_free (matrix);
         GST_ERROR_OBJECT (s, "mix-matrix is %u x %u, the caps have %d input and %d output channels", rows, cols, ai.channels, ao.channels);
         return FALSE;
       }
       for (r = 0; r < rows; r++)
         for (c = 0; c < cols; c++) {
           const GValue *v = gst_value_array_get_value (gst_value_array_get_value (&s->mix_matrix, r), c);
-          cfg.mix_matrix[r][c] = G_VALUE_HOLDS_FLOAT (v) ? g_value_get_float (v) : G_VALUE_HOLDS_DOUBLE (v) ? (float) g_value_get_double (v) :
+          matrix[r * cols + c] = G_VALUE_HOLDS_FLOAT (v) ? g_value_get_float (v) : G_VALUE_HOLDS_DOUBLE (v) ? (float) g_value_get_double (v) :
               G_VALUE_HOLDS_INT (v) ? (float) g_value_get_int (v) : 0.0f;
         }
     }
   }
   GST_OBJECT_UNLOCK (s);
-  s->conv = gstamd_audio_converter_new_layouts (0, &ai, amd_ac_layout (&s->in), &ao, amd_ac_layout (&s->out), &cfg, &status);
+  wide = ai.channels > GSTAMD_AUDIO_MAX_CHANNELS || ao.channels > GSTAMD_AUDIO_MAX_CHANNELS;
+  GST_DEBUG_OBJECT (s, "converter of %d -> %d channels through %s", ai.channels, ao.channels,
+      wide ? "gstamd_audio_converter_new_wide" : "gstamd_audio_converter_new_layouts");
+  if (wide) {
+    s->conv = gstamd_audio_converter_new_wide (0, &ai, amd_ac_layout (&s->in), &ao, amd_ac_layout (&s->out), &cfg, matrix, &status);
+  } else {
+    GstAmdAudioInfo ni, no;
+    gint r, c;
+    amd_ac_info_narrow (&ai, &ni);
+    amd_ac_info_narrow (&ao, &no);
+    cfg.has_mix_matrix = matrix != NULL;
+    for (r = 0; matrix && r < ao.channels; r++)
+      for (c = 0; c < ai.channels; c++)
+        cfg.mix_matrix[r][c] = matrix[r * ai.channels + c];
+    s->conv = gstamd_audio_converter_new_layouts (0, &ni, amd_ac_layout (&s->in), &no, amd_ac_layout (&s->out), &cfg, &status);
+  }
+  g_free (matrix);
   if (!s->conv) {
     GST_ERROR_OBJECT (s, "Failed to make converter (status %d): %s", status, gstamd_last_error ());
     return FALSE;
