@@ -264,6 +264,10 @@ def _conv_lib():
         L.gstamd_audio_converter_is_passthrough.argtypes = [C.c_void_p]
         L.gstamd_audio_converter_samples.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         L.gstamd_audio_converter_get_mix_matrix.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int]
+        if hasattr(L, "gstamd_audio_converter_samples_many"):    # (absent from an older build loaded through GSTAMD_LIB_PATH as a baseline: convert_many raises there)
+            L.gstamd_audio_converter_samples_many.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_void_p]
+            L.gstamd_audio_converter_debug_many.argtypes = [C.POINTER(C.c_int32), C.c_int]
         _conv_ready = True
     return L
 
@@ -350,3 +354,33 @@ class AudioConverterWide(AudioConverter):
                                                               C.byref(config) if config is not None else None, wide_matrix(mix_matrix), C.byref(st))
         if not self._h:
             raise _v.GstAmdError(st.value, _v.last_error())
+
+
+class ManyConversions:
+    """The argument arrays of one gstamd_audio_converter_samples_many call, built once (as ManyBuffers is for the resampler).  converters: AudioConverter
+    objects (None entries are passed as NULL, for the call to refuse); srcs: buffers, None for silence, or None for a NULL array."""
+
+    def __init__(self, converters, srcs, in_frames, dsts, out_frames):
+        n = self.n = len(converters)
+        assert n == len(in_frames) == len(dsts) == len(out_frames) and (srcs is None or n == len(srcs))
+        self.keep = (list(converters), None if srcs is None else list(srcs), list(dsts))
+        self.cs = (C.c_void_p * n)(*[None if c is None else c._h for c in converters])
+        self.ip = None if srcs is None else (C.c_void_p * n)(*[None if x is None else _ptr(x) for x in srcs])
+        self.op = (C.c_void_p * n)(*[None if x is None else _ptr(x) for x in dsts])
+        self.inf = (C.c_size_t * n)(*in_frames)
+        self.outf = (C.c_size_t * n)(*out_frames)
+
+    def run(self, stream=None):
+        _v._check(_conv_lib().gstamd_audio_converter_samples_many(self.n, self.cs, 0, self.ip, self.inf, self.op, self.outf, stream))
+
+
+def convert_many(converters, srcs, in_frames, dsts, out_frames, stream=None):
+    """gstamd_audio_converter_samples_many: one buffer per converter; consecutive converters made with equal arguments share their launches"""
+    ManyConversions(converters, srcs, in_frames, dsts, out_frames).run(stream)
+
+
+def convert_many_debug():
+    """what this thread's last convert_many did (gstamd_audio_converter_debug_many)"""
+    buf = (C.c_int32 * 4)()
+    _conv_lib().gstamd_audio_converter_debug_many(buf, 4)
+    return dict(zip(("runs", "batched", "single", "launches"), list(buf)))

@@ -130,6 +130,28 @@ __global__ __launch_bounds__ (64) void k_aconv_wide_shape_planes (AConvPlan p, c
     aconv_shape_planes_of<K> (p, qv, qd, hist, dst);
 }
 
+// ---- many converters of one plan (gstamd_audio_converter_samples_many): blockIdx.y is the stream, blockIdx.x / the lane
+// do what the stream's own k_aconv_pre / k_aconv_post launch would; the grid's x extent is the longest stream's, so the blocks past a
+// shorter stream's lanes return at once.  The tables are indexed by blockIdx alone: scalar loads from the kernel arguments.
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_pre_many (AConvPlan p, AConvManyPreTable many)
+{
+  aconv_pre_many_lane<K> (p, many.s[blockIdx.y], (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_post_many (AConvPlan p, const AConvJump *__restrict__ jump, AConvManyPostTable many)
+{
+  aconv_post_many_lane<K> (p, *jump, many.s[blockIdx.y], (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// one 64-lane workgroup per stream, a lane per channel: the recurrences of all streams' channels walk at the same time
+template <int K>
+__global__ __launch_bounds__ (64) void k_aconv_shape_many (AConvPlan p, AConvManyShapeTable many)
+{
+  aconv_shape_many_lane<K> (p, many.s[blockIdx.x], (int) threadIdx.x);
+}
+
 static unsigned aconv_blocks (const AConvSplit &s) { return (unsigned) ((aconv_split_lanes (s) + 255) / 256); }
 
 struct GstAmdAudioConverter {
@@ -585,6 +607,155 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
   for (int k = 0; k < (c->out_layout ? c->plan.out_ch : 1); k++)
     op[k] = (uint8_t *) out + (size_t) k * out_plane;
   return aconv_run (c, in ? ip : nullptr, in_frames, op, out_frames, (hipStream_t) stream);
+}
+
+/* ---- gstamd_audio_converter_samples_many -------------------------------------------------------------------------------- */
+/* the calling thread's last call: batched runs, streams served by them, streams gone one by one, launches of the batched converter kernels */
+static thread_local int32_t aconv_many_debug[4] = { 0, 0, 0, 0 };
+
+/* a run (aconv_many_run_length) of `run` >= 2 converters of one plan: aconv_run's stages, each as one launch over all of them */
+static int aconv_run_many (int run, GstAmdAudioConverter *const *cs, const uint8_t *const *in, const size_t *in_frames, uint8_t *const *out,
+    const size_t *out_frames, hipStream_t stream)
+{
+  const AConvPlan &p = cs[0]->plan;
+  const size_t mid_bytes_in = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
+  const bool shape = aconv_plan_shapes (p), resample = cs[0]->resampler != nullptr;
+  int r;
+  /* every allocation before the first launch */
+  for (int k = 0; k < run; k++) {
+    GstAmdAudioConverter *c = cs[k];
+    if ((r = ensure (&c->mid_a, &c->mid_a_size, in_frames[k] * mid_bytes_in)) != GSTAMD_OK)
+      return r;
+    if (resample && (r = ensure (&c->mid_b, &c->mid_b_size, (out_frames[k] ? out_frames[k] : 1) * mid_bytes_in)) != GSTAMD_OK)
+      return r;
+    /* the samples and, behind them, the dither words (q_d stays the single-stream path's) */
+    if (shape && out_frames[k] && (r = ensure (&c->q_v, &c->q_v_size, out_frames[k] * (size_t) p.out_ch * 8)) != GSTAMD_OK)
+      return r;
+  }
+  {
+    AConvManyPreTable t;
+    memset ((void *) &t, 0, sizeof (t));
+    size_t lanes = 0;
+    for (int k = 0; k < run; k++) {
+      const size_t l = aconv_many_pre_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
+      lanes = l > lanes ? l : lanes;
+    }
+#define PRE(K) k_aconv_pre_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+    aconv_many_debug[3]++;
+  }
+  if (resample) {
+    GstAmdAudioResampler *rs[GSTAMD_ACONV_MANY_MAX];
+    const void *ri[GSTAMD_ACONV_MANY_MAX];
+    void *ro[GSTAMD_ACONV_MANY_MAX];
+    for (int k = 0; k < run; k++) {
+      rs[k] = cs[k]->resampler;
+      ri[k] = cs[k]->mid_a;
+      ro[k] = cs[k]->mid_b;
+    }
+    /* one launch where the filter qualifies, per stream where it does not: its own decision */
+    if ((r = gstamd_audio_resampler_resample_many (run, rs, ri, in_frames, ro, out_frames, stream)) != GSTAMD_OK)
+      return r;
+  }
+  AConvManyPostTable t;
+  AConvManyShapeTable sh;
+  memset ((void *) &t, 0, sizeof (t));
+  memset ((void *) &sh, 0, sizeof (sh));
+  size_t lanes = 0;
+  for (int k = 0; k < run; k++) {
+    GstAmdAudioConverter *c = cs[k];
+    int32_t *q = shape && out_frames[k] ? (int32_t *) c->q_v : nullptr;
+    const size_t l = aconv_many_post_entry (p, c->dither, resample ? c->mid_b : c->mid_a, out[k], out_frames[k], q, &t.s[k]);
+    lanes = l > lanes ? l : lanes;
+    sh.s[k] = { q, c->hist, out[k], out_frames[k] };
+  }
+  if (lanes) {                                  /* 0: every resampler of the run only took input into its history */
+#define POST(K) k_aconv_post_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, cs[0]->jump_dev, t)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+    aconv_many_debug[3]++;
+    if (shape) {
+#define SHAPE(K) k_aconv_shape_many<K><<<dim3 ((unsigned) run), dim3 (64), 0, stream>>> (p, sh)
+      GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+      aconv_many_debug[3]++;
+    }
+  }
+  if (hipGetLastError () != hipSuccess)
+    return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
+  for (int k = 0; k < run; k++)
+    aconv_dither_advance (p, cs[k]->jump_host, &cs[k]->dither, out_frames[k] * (size_t) p.out_ch);
+  return GSTAMD_OK;
+}
+
+int gstamd_audio_converter_samples_many (int n, GstAmdAudioConverter *const *converters, int flags, const void *const *in, const size_t *in_frames,
+    void *const *out, const size_t *out_frames, void *stream)
+{
+  memset (aconv_many_debug, 0, sizeof (aconv_many_debug));
+  if (n < 0 || (n > 0 && (!converters || !in_frames || !out_frames)))
+    return aconv_fail (GSTAMD_ERR_INVALID, "NULL argument array");
+  /* everything that can refuse a stream, for all of them, before anything is launched: what gstamd_audio_converter_samples checks */
+  for (int i = 0; i < n; i++) {
+    const GstAmdAudioConverter *c = converters[i];
+    if (!c || (out_frames[i] && (!out || !out[i])))
+      return aconv_fail (GSTAMD_ERR_INVALID, "NULL converter or output");
+    if (in_frames[i] == 0)
+      continue;
+    if (!c->resampler && !(in && in[i]))
+      return aconv_fail (GSTAMD_ERR_INVALID, "NULL input");
+    if (!c->resampler && !c->passthrough && in_frames[i] != out_frames[i])
+      return aconv_fail (GSTAMD_ERR_INVALID, "in_frames != out_frames without a resampler");
+  }
+  std::vector<AConvManyItem> items;
+  std::vector<int> at;                          /* items[j] is stream at[j] of the call: the streams with in_frames == 0 are skipped here */
+  items.reserve ((size_t) n);
+  at.reserve ((size_t) n);
+  for (int i = 0; i < n; i++) {
+    const GstAmdAudioConverter *c = converters[i];
+    if (in_frames[i] == 0)
+      continue;
+    items.push_back ({ &c->plan, c, !c->wide && !c->in_layout && !c->out_layout && !c->passthrough, c->resampler != nullptr, in && in[i] != nullptr,
+        in_frames[i], out_frames[i] });
+    at.push_back (i);
+  }
+  const int live = (int) items.size ();
+  for (int done = 0; done < live;) {
+    const int run = aconv_many_run_length (&items[(size_t) done], live - done);
+    int r;
+    if (run < 2) {
+      const int i = at[(size_t) done];
+      r = gstamd_audio_converter_samples (converters[i], flags, in ? in[i] : nullptr, in_frames[i], out ? out[i] : nullptr, out_frames[i], stream);
+      aconv_many_debug[2]++;
+    } else {
+      GstAmdAudioConverter *cs[GSTAMD_ACONV_MANY_MAX];
+      const uint8_t *ip[GSTAMD_ACONV_MANY_MAX];
+      uint8_t *op[GSTAMD_ACONV_MANY_MAX];
+      size_t inf[GSTAMD_ACONV_MANY_MAX], outf[GSTAMD_ACONV_MANY_MAX];
+      for (int k = 0; k < run; k++) {
+        const int i = at[(size_t) (done + k)];
+        cs[k] = converters[i];
+        ip[k] = (const uint8_t *) in[i];
+        op[k] = out ? (uint8_t *) out[i] : nullptr;
+        inf[k] = in_frames[i];
+        outf[k] = out_frames[i];
+      }
+      r = aconv_run_many (run, cs, ip, inf, op, outf, (hipStream_t) stream);
+      aconv_many_debug[0]++;
+      aconv_many_debug[1] += run;
+    }
+    if (r != GSTAMD_OK)
+      return r;
+    done += run;
+  }
+  return GSTAMD_OK;
+}
+
+int gstamd_audio_converter_debug_many (int32_t *out, int max_out)
+{
+  for (int i = 0; out && i < 4 && i < max_out; i++)
+    out[i] = aconv_many_debug[i];
+  return 4;
 }
 
 }  // extern "C"

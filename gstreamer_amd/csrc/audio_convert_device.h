@@ -1326,6 +1326,84 @@ inline AConvSplit aconv_swap_split (const void *in, const void *out, int bytes, 
   return aconv_split (in, bytes, n, (((uintptr_t) in ^ (uintptr_t) out) & 3u) == 0);
 }
 
+// ---- many converters of one plan in one set of launches (gstamd_audio_converter_samples_many) --------------------------
+// blockIdx.y (for the shaping kernel blockIdx.x) is the stream.  What differs between two streams of a plan - buffers, how the lanes share
+// them, where the dither generator stands - comes by value in the kernel arguments, one table per kernel, read with an index that is
+// uniform over the workgroup.  64 entries have to fit 4 KB beside the 664 bytes of the plan, so an entry holds no more than its kernel
+// needs: an AConvSplit is packed into eight bytes, and a stream's dither words follow its samples in one buffer (q, q + n).
+#define GSTAMD_ACONV_MANY_MAX 64
+
+struct AConvSplitPacked {
+  uint64_t v;                   // bits 0 .. 39: n (a stream of a run has fewer than 2^30 frames of at most 8 channels); 40 .. 41: head; 42: grouped
+};
+
+GSTAMD_AC AConvSplitPacked aconv_split_pack (const AConvSplit &s)
+{
+  return { (uint64_t) s.n | ((uint64_t) s.head << 40) | ((uint64_t) (s.groups ? 1 : 0) << 42) };
+}
+
+GSTAMD_AC AConvSplit aconv_split_unpack (AConvSplitPacked k)
+{
+  AConvSplit s = { 0, 0, (size_t) (k.v & 0xffffffffffull) };
+  if ((k.v >> 42) & 1u) {
+    s.head = (size_t) ((k.v >> 40) & 3u);
+    s.groups = (s.n - s.head) / 4;
+  }
+  return s;
+}
+
+struct AConvManyPre {           // 24 bytes
+  const uint8_t *in;
+  uint8_t *mid;
+  AConvSplitPacked split;
+};
+
+struct AConvManyPost {          // 48 bytes
+  const uint8_t *mid;
+  uint8_t *out;
+  int32_t *q;                   // with noise shaping: split.n S32 samples, then as many dither words
+  AConvSplitPacked split;       // n == 0: the resampler only took history - no lanes, no draws
+  AConvDitherState ds;
+  int pad;
+};
+
+struct AConvManyShape {         // 32 bytes
+  const int32_t *q;
+  int32_t *hist;
+  uint8_t *out;
+  size_t frames;
+};
+
+struct AConvManyPreTable { AConvManyPre s[GSTAMD_ACONV_MANY_MAX]; };
+struct AConvManyPostTable { AConvManyPost s[GSTAMD_ACONV_MANY_MAX]; };
+struct AConvManyShapeTable { AConvManyShape s[GSTAMD_ACONV_MANY_MAX]; };
+static_assert (sizeof (AConvManyPre) == 24 && sizeof (AConvManyPost) == 48 && sizeof (AConvManyShape) == 32, "entries of the tables");
+static_assert (sizeof (AConvPlan) + sizeof (void *) + sizeof (AConvManyPostTable) <= 3840, "kernel arguments end at 4 KB");
+
+// lane t of stream m: the lane of the stream's own k_aconv_pre / k_aconv_post launch; lanes past a shorter stream's end do nothing
+template <int K> GSTAMD_AC void aconv_pre_many_lane (const AConvPlan &p, const AConvManyPre &m, size_t t)
+{
+  const AConvSplit s = aconv_split_unpack (m.split);
+  if (t >= aconv_split_lanes (s))
+    return;
+  aconv_pre_lane<K> (p, m.in, m.mid, s, t);
+}
+
+template <int K> GSTAMD_AC void aconv_post_many_lane (const AConvPlan &p, const AConvJump &jump, const AConvManyPost &m, size_t t)
+{
+  const AConvSplit s = aconv_split_unpack (m.split);
+  if (t >= aconv_split_lanes (s))
+    return;
+  aconv_post_lane<K> (p, jump, m.ds, m.mid, m.out, m.q, m.q ? m.q + s.n : nullptr, s, t);
+}
+
+// lane c of stream m's 64-lane workgroup: one channel's error recurrence, all streams' channels side by side
+template <int K> GSTAMD_AC void aconv_shape_many_lane (const AConvPlan &p, const AConvManyShape &m, int c)
+{
+  if (c < p.out_ch && m.frames)
+    aconv_shape_channel<K> (p, m.q, m.q + m.frames * (size_t) p.out_ch, m.hist, m.out, m.frames, c);
+}
+
 #ifndef __HIPCC__
 // ---- one sample at a time with the container looked up per call: the entry points of a host loop that walks samples, not lanes
 // (tests/emu/emu_audio.cpp).  The kernels never come here.  For the endian plan the first stage parks the container in the sample's mid

@@ -452,4 +452,63 @@ inline int aconv_make_plan_wide (int flags, const GstAmdAudioInfoWide *in, int i
       (int *) plan->mi.data (), out->channels, plan->use.data (), resample, passthrough, err);
 }
 
+// ---- gstamd_audio_converter_samples_many: which streams of a call share a set of launches --------------------------------
+// One stream of the call as the decision sees it.  Streams with in_frames == 0 are skipped before the walk ("skipping empty buffer"): they
+// do nothing, so they neither belong to a run nor end one.
+struct AConvManyItem {
+  const AConvPlan *plan;
+  const void *id;               // the converter: the same one twice in a run would make its second buffer depend on its first
+  bool ordinary;                // not wide, both layouts interleaved, not passthrough (the endian plan is read from the plan)
+  bool resampler;               // a resampler sits between the two kernels
+  bool has_input;               // in[i] != NULL
+  size_t in_frames, out_frames;
+};
+
+inline bool aconv_many_batchable (const AConvManyItem &a)
+{
+  return a.ordinary && !a.plan->endian_swap && a.has_input && a.in_frames > 0 && a.in_frames < ((size_t) 1 << 30) && a.out_frames < ((size_t) 1 << 30);
+}
+
+// The run that starts at it[0]: how many consecutive streams (at most GSTAMD_ACONV_MANY_MAX) one set of launches serves.  1: it[0] goes
+// through the single-stream path by itself - because it does not qualify, or because its neighbour does not join it.
+inline int aconv_many_run_length (const AConvManyItem *it, int n)
+{
+  if (n < 1)
+    return 0;
+  if (!aconv_many_batchable (it[0]))
+    return 1;
+  int run = 1;
+  while (run < n && run < GSTAMD_ACONV_MANY_MAX) {
+    const AConvManyItem &a = it[run];
+    /* (an AConvPlan is zero-filled before it is made and has no padding: equal bytes are equal fields, matrices included) */
+    if (!aconv_many_batchable (a) || a.resampler != it[0].resampler || memcmp (a.plan, it[0].plan, sizeof (AConvPlan)) != 0)
+      break;
+    bool dup = false;
+    for (int k = 0; k < run; k++)
+      dup = dup || it[k].id == a.id;
+    if (dup)
+      break;
+    run++;
+  }
+  return run;
+}
+
+// a stream's entries in the tables of the batched kernels; each returns the stream's lanes.  The splits are those of aconv_run's own
+// launches: computed per stream, since every caller buffer has its own byte phase.
+inline size_t aconv_many_pre_entry (const AConvPlan &p, const uint8_t *in, size_t in_frames, uint8_t *mid, AConvManyPre *e)
+{
+  const AConvSplit s = aconv_split (in, afmt_bytes (p.in_fmt), in_frames * (size_t) p.out_ch, aconv_pre_grouped (p));
+  *e = { in, mid, aconv_split_pack (s) };
+  return aconv_split_lanes (s);
+}
+
+inline size_t aconv_many_post_entry (const AConvPlan &p, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, size_t out_frames, int32_t *q, AConvManyPost *e)
+{
+  const AConvSplit s = aconv_split (out, afmt_bytes (p.out_fmt), out_frames * (size_t) p.out_ch, aconv_post_grouped (p));
+  *e = { mid, out, q, aconv_split_pack (s), ds, 0 };
+  return aconv_split_lanes (s);
+}
+
+inline bool aconv_plan_shapes (const AConvPlan &p) { return p.ns && p.quant_shift > 0; }
+
 }  // namespace gstamd

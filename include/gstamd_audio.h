@@ -158,7 +158,7 @@ typedef struct GstAmdAudioInfoWide {
 
 typedef struct GstAmdAudioConverterConfig {
   int32_t dither_method;        /* GstAudioConverter.dither-method (library default: none) */
-  int32_t noise_shaping;        /* GstAudioConverter.noise-shaping-method (NONE; the error-feedback methods are sequential per channel) */
+  int32_t noise_shaping;        /* GstAudioConverter.noise-shaping-method (library default: NONE; 1 error-feedback, 2 simple, 3 medium, 4 high - one lane per channel walks the recurrence) */
   uint32_t dither_threshold;    /* GstAudioConverter.dither-threshold (20) */
   int32_t resampler_method;     /* GstAudioConverter.resampler-method (BLACKMAN_NUTTALL = 3) */
   int32_t has_resampler_options;
@@ -206,6 +206,20 @@ int gstamd_audio_converter_samples_planes (GstAmdAudioConverter *convert, int fl
     void *const out[], size_t out_frames, void *stream);
 /* the mix matrix the converter uses, matrix[in][out] as GstAudioChannelMixer holds it; returns in_channels * out_channels */
 int gstamd_audio_converter_get_mix_matrix (GstAmdAudioConverter *convert, float *matrix, int max);
+/* n independent converters, one buffer each, in as few launches as their plans allow.  Outputs and converter states
+ * are exactly those of n gstamd_audio_converter_samples calls made in array order.  No reference counterpart.
+ * in[i] / out[i] are what gstamd_audio_converter_samples takes for converters[i]; in == NULL or in[i] == NULL feeds silence;
+ * in_frames[i] == 0 skips that stream.  Everything is validated before anything is launched: a NULL converter, a NULL out[i] with
+ * out_frames[i] > 0, a NULL input or in_frames[i] != out_frames[i] for a converter without a resampler return GSTAMD_ERR_INVALID with
+ * nothing done.  Consecutive converters (up to 64) made with equal arguments - interleaved on both sides, 8 channels or fewer, not a
+ * passthrough or a byte swap, non-NULL input, fewer than 2^30 frames - share one first kernel, one gstamd_audio_resampler_resample_many,
+ * one second kernel and one noise shaping kernel; every other one, and the same converter a second time, goes through
+ * the single-stream path in its place in the order.  The buffers of different streams must not overlap. */
+int gstamd_audio_converter_samples_many (int n, GstAmdAudioConverter *const *converters, int flags, const void *const *in,
+    const size_t *in_frames, void *const *out, const size_t *out_frames, void *stream);
+/* for tests: what the calling thread's last gstamd_audio_converter_samples_many did - { batched runs, streams served by batched runs,
+ * streams gone one by one, launches of the batched converter kernels (the resampler's own not counted) }; returns 4 */
+int gstamd_audio_converter_debug_many (int32_t *out, int max_out);
 
 #ifdef __cplusplus
 }
