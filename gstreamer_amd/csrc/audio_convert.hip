@@ -152,6 +152,55 @@ __global__ __launch_bounds__ (64) void k_aconv_shape_many (AConvPlan p, AConvMan
   aconv_shape_many_lane<K> (p, many.s[blockIdx.x], (int) threadIdx.x);
 }
 
+// ---- the same for converters with a non-interleaved side and for wide ones.  A side of a stream is 16 bytes (one pointer,
+// the planes frames * bytes apart), which the lane bodies of k_aconv_pre_planes / _post_planes / _shape_planes take as an AConvPlanesEven;
+// since that struct has no pointer array it serves 64 channels as well as 8, and k_aconv_wide_post_planes / _shape_planes need no batched
+// form of their own.  blockIdx.y: the row (an output channel), blockIdx.z: the stream.
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_pre_planes_many (AConvPlan p, AConvManyPrePlanesTable many)
+{
+  aconv_pre_planes_many_lane<K> (p, many.s[blockIdx.z], (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_pre_mix_many (AConvPlan p, AConvManyPreTable many)
+{
+  aconv_pre_mix_many_lane<K> (p, many.s[blockIdx.z], (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_post_planes_many (AConvPlan p, const AConvJump *__restrict__ jump, AConvManyPostPlanesTable many)
+{
+  aconv_post_planes_many_lane<K> (p, *jump, many.s[blockIdx.z], (int) blockIdx.y, (size_t) blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// ONE workgroup of 64 lanes, lane = stream: a stream's planes are one recurrence, so the 64 recurrences of a run walk side by side in one
+// wave.  (The table is indexed by the lane here: vector loads from the kernel arguments; the entries past the run are zero.)
+template <int K>
+__global__ __launch_bounds__ (64) void k_aconv_shape_planes_many (AConvPlan p, AConvManyShapeTable many)
+{
+  aconv_shape_planes_many_lane<K> (p, many.s[threadIdx.x]);
+}
+
+// k_aconv_wide_mix with blockIdx.y = stream; a workgroup past its stream's last tile leaves as a whole before the barrier.  The matrix is
+// the first converter's: aconv_many_run_length lets only converters of equal matrices share a run.
+template <int K>
+__global__ __launch_bounds__ (256) void k_aconv_wide_mix_many (AConvPlan p, AConvWideMatrix w, AConvManyPrePlanesTable many, int in_planar, int tile)
+{
+  extern __shared__ __attribute__ ((aligned (16))) unsigned char aconv_wide_lds[];
+  const AConvManyPrePlanes &m = many.s[blockIdx.y];
+  size_t n0;
+  int nf;
+  if (!aconv_wide_many_tile (m, (size_t) blockIdx.x, tile, &n0, &nf))
+    return;
+  uint8_t *x = aconv_wide_lds, *mat = aconv_wide_lds + aconv_wide_x_bytes (p, tile);
+  if (p.mix)
+    aconv_wide_stage_matrix (p, w, mat, (int) threadIdx.x, 256);
+  aconv_wide_stage_lane<K> (p, aconv_many_side (m.in, akind_bytes (K)), in_planar, n0, nf, x, (int) threadIdx.x, 256);
+  __syncthreads ();
+  aconv_wide_mix_lane (p, x, mat, w.use, m.mid, n0, nf, (int) threadIdx.x, 256);
+}
+
 static unsigned aconv_blocks (const AConvSplit &s) { return (unsigned) ((aconv_split_lanes (s) + 255) / 256); }
 
 struct GstAmdAudioConverter {
@@ -613,13 +662,14 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
 /* the calling thread's last call: batched runs, streams served by them, streams gone one by one, launches of the batched converter kernels */
 static thread_local int32_t aconv_many_debug[4] = { 0, 0, 0, 0 };
 
-/* a run (aconv_many_run_length) of `run` >= 2 converters of one plan: aconv_run's stages, each as one launch over all of them */
+/* a run (aconv_many_run_length) of `run` >= 2 converters of one plan, layout pair and kind: aconv_run's stages, each as one launch over all of them */
 static int aconv_run_many (int run, GstAmdAudioConverter *const *cs, const uint8_t *const *in, const size_t *in_frames, uint8_t *const *out,
     const size_t *out_frames, hipStream_t stream)
 {
   const AConvPlan &p = cs[0]->plan;
   const size_t mid_bytes_in = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
   const bool shape = aconv_plan_shapes (p), resample = cs[0]->resampler != nullptr;
+  const int out_layout = cs[0]->out_layout;
   int r;
   /* every allocation before the first launch */
   for (int k = 0; k < run; k++) {
@@ -632,19 +682,63 @@ static int aconv_run_many (int run, GstAmdAudioConverter *const *cs, const uint8
     if (shape && out_frames[k] && (r = ensure (&c->q_v, &c->q_v_size, out_frames[k] * (size_t) p.out_ch * 8)) != GSTAMD_OK)
       return r;
   }
-  {
-    AConvManyPreTable t;
-    memset ((void *) &t, 0, sizeof (t));
-    size_t lanes = 0;
-    for (int k = 0; k < run; k++) {
-      const size_t l = aconv_many_pre_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
-      lanes = l > lanes ? l : lanes;
-    }
-#define PRE(K) k_aconv_pre_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, t)
-    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+  switch (aconv_many_first (p, cs[0]->wide, cs[0]->in_layout, out_layout)) {
+    case ACONV_FIRST_WIDE: {
+      AConvManyPrePlanesTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      const int tile = aconv_wide_tile_frames (p.in_ch, p.out_ch);
+      const size_t lds = aconv_wide_lds_bytes (p, tile);        /* of the plan: one value for the launch */
+      size_t tiles = 0;
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_wide_entry (in[k], in_frames[k], cs[k]->mid_a, tile, &t.s[k]);
+        tiles = l > tiles ? l : tiles;
+      }
+#define PRE(K) k_aconv_wide_mix_many<K><<<dim3 ((unsigned) tiles, (unsigned) run), dim3 (256), lds, stream>>> (p, cs[0]->wide_dev, t, cs[0]->in_layout, tile)
+      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
 #undef PRE
-    aconv_many_debug[3]++;
+      break;
+    }
+    case ACONV_FIRST_PLANES: {
+      AConvManyPrePlanesTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      size_t lanes = 0;
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_pre_planes_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
+        lanes = l > lanes ? l : lanes;
+      }
+#define PRE(K) k_aconv_pre_planes_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+      break;
+    }
+    case ACONV_FIRST_MIX: {
+      AConvManyPreTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      size_t lanes = 0;
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_pre_mix_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
+        lanes = l > lanes ? l : lanes;
+      }
+#define PRE(K) k_aconv_pre_mix_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+      break;
+    }
+    default: {
+      AConvManyPreTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      size_t lanes = 0;
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_pre_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
+        lanes = l > lanes ? l : lanes;
+      }
+#define PRE(K) k_aconv_pre_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+      break;
+    }
   }
+  aconv_many_debug[3]++;
   if (resample) {
     GstAmdAudioResampler *rs[GSTAMD_ACONV_MANY_MAX];
     const void *ri[GSTAMD_ACONV_MANY_MAX];
@@ -658,28 +752,53 @@ static int aconv_run_many (int run, GstAmdAudioConverter *const *cs, const uint8
     if ((r = gstamd_audio_resampler_resample_many (run, rs, ri, in_frames, ro, out_frames, stream)) != GSTAMD_OK)
       return r;
   }
-  AConvManyPostTable t;
   AConvManyShapeTable sh;
-  memset ((void *) &t, 0, sizeof (t));
   memset ((void *) &sh, 0, sizeof (sh));
   size_t lanes = 0;
-  for (int k = 0; k < run; k++) {
-    GstAmdAudioConverter *c = cs[k];
-    int32_t *q = shape && out_frames[k] ? (int32_t *) c->q_v : nullptr;
-    const size_t l = aconv_many_post_entry (p, c->dither, resample ? c->mid_b : c->mid_a, out[k], out_frames[k], q, &t.s[k]);
-    lanes = l > lanes ? l : lanes;
-    sh.s[k] = { q, c->hist, out[k], out_frames[k] };
-  }
-  if (lanes) {                                  /* 0: every resampler of the run only took input into its history */
-#define POST(K) k_aconv_post_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, cs[0]->jump_dev, t)
-    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+  if (out_layout) {
+    AConvManyPostPlanesTable t;
+    memset ((void *) &t, 0, sizeof (t));
+    for (int k = 0; k < run; k++) {
+      GstAmdAudioConverter *c = cs[k];
+      int32_t *q = shape && out_frames[k] ? (int32_t *) c->q_v : nullptr;
+      const size_t l = aconv_many_post_planes_entry (p, c->dither, resample ? c->mid_b : c->mid_a, out[k], out_frames[k], q, &t.s[k]);
+      lanes = l > lanes ? l : lanes;
+      sh.s[k] = { q, c->hist, out[k], out_frames[k] };
+    }
+    if (lanes) {
+#define POST(K) k_aconv_post_planes_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, \
+    cs[0]->jump_dev, t)
+      GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
 #undef POST
-    aconv_many_debug[3]++;
-    if (shape) {
-#define SHAPE(K) k_aconv_shape_many<K><<<dim3 ((unsigned) run), dim3 (64), 0, stream>>> (p, sh)
-      GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
-#undef SHAPE
       aconv_many_debug[3]++;
+      if (shape) {
+#define SHAPE(K) k_aconv_shape_planes_many<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, sh)
+        GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+        aconv_many_debug[3]++;
+      }
+    }
+  } else {
+    AConvManyPostTable t;
+    memset ((void *) &t, 0, sizeof (t));
+    for (int k = 0; k < run; k++) {
+      GstAmdAudioConverter *c = cs[k];
+      int32_t *q = shape && out_frames[k] ? (int32_t *) c->q_v : nullptr;
+      const size_t l = aconv_many_post_entry (p, c->dither, resample ? c->mid_b : c->mid_a, out[k], out_frames[k], q, &t.s[k]);
+      lanes = l > lanes ? l : lanes;
+      sh.s[k] = { q, c->hist, out[k], out_frames[k] };
+    }
+    if (lanes) {                                /* 0: every resampler of the run only took input into its history */
+#define POST(K) k_aconv_post_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, cs[0]->jump_dev, t)
+      GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+      aconv_many_debug[3]++;
+      if (shape) {
+#define SHAPE(K) k_aconv_shape_many<K><<<dim3 ((unsigned) run), dim3 (64), 0, stream>>> (p, sh)
+        GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+        aconv_many_debug[3]++;
+      }
     }
   }
   if (hipGetLastError () != hipSuccess)
@@ -716,7 +835,7 @@ int gstamd_audio_converter_samples_many (int n, GstAmdAudioConverter *const *con
     if (in_frames[i] == 0)
       continue;
     items.push_back ({ &c->plan, c, !c->wide && !c->in_layout && !c->out_layout && !c->passthrough, c->resampler != nullptr, in && in[i] != nullptr,
-        in_frames[i], out_frames[i] });
+        in_frames[i], out_frames[i], true, c->passthrough, c->wide, c->in_layout, c->out_layout, c->wide ? &c->wide_plan : nullptr });
     at.push_back (i);
   }
   const int live = (int) items.size ();

@@ -330,6 +330,39 @@ GSTAMD_AC size_t aconv_split_single (const AConvSplit &s, size_t t)
   return k < s.head ? k : k + 4 * s.groups;
 }
 
+// head of aconv_split's grouped form for n samples at q, or 4 where no lane of four samples fits: the same decision on the device
+GSTAMD_AC int aconv_head_at (const uint8_t *q, int bytes, size_t n)
+{
+  int h = 0;
+  while (h < 4 && (((uintptr_t) q + (size_t) (bytes * h)) & 3u))
+    h++;
+  return h == 4 || n < (size_t) h + 4 ? 4 : h;
+}
+
+// A non-interleaved side as gstamd_audio_converter_samples takes it: ONE pointer, the planes frames * bytes apart.  No pointer array,
+// so it is made in registers from a 16-byte table entry (AConvManySide) and serves any channel count.  how: 0 .. 4 is the
+// head of every row (a mixing first kernel: aconv_planes_heads' "same" rule, decided on the host); AConvPlanesEven::OWN: row y works on
+// plane y alone and takes the head of that plane's address.
+struct AConvPlanesEven {
+  enum { OWN = 5 };
+  uint8_t *base;
+  size_t frames;
+  int bytes;                    // of a sample
+  int how;
+  int realign;                  // as in AConvPlanes
+};
+
+// what the lane bodies ask of a planes struct beside .frames and .realign
+GSTAMD_AC uint8_t *aconv_plane_ptr (const AConvPlanes &pl, int c) { return pl.p[c]; }
+GSTAMD_AC uint8_t *aconv_plane_ptr (const AConvPlanesWide &pl, int c) { return pl.p[c]; }
+GSTAMD_AC uint8_t *aconv_plane_ptr (const AConvPlanesEven &pl, int c) { return pl.base + (size_t) c * pl.frames * (size_t) pl.bytes; }
+GSTAMD_AC int aconv_plane_head (const AConvPlanes &pl, int y) { return pl.head[y]; }
+GSTAMD_AC int aconv_plane_head (const AConvPlanesWide &pl, int y) { return pl.head[y]; }
+GSTAMD_AC int aconv_plane_head (const AConvPlanesEven &pl, int y)
+{
+  return pl.how == AConvPlanesEven::OWN ? aconv_head_at (aconv_plane_ptr (pl, y), pl.bytes, pl.frames) : pl.how;
+}
+
 // ---- unpack / pack (audio-format.c unpack_* / pack_*, gstaudiopack.orc) ------------------------------------------------------------------
 // do_unpack passes GST_AUDIO_PACK_FLAG_TRUNCATE_RANGE (audio-converter.c:477): the *_trunc programs, plain shifts.  Integer container w
 // of depth d -> S32: w << (32 - d), sign bit flipped for the unsigned formats; container bits above the depth fall off the top.
@@ -585,10 +618,11 @@ struct AConvSrcFrames {
   GSTAMD_AC const uint8_t *at (const AConvPlan &p, int bytes, size_t n, int ci) const { return in + (size_t) bytes * (n * (size_t) p.in_ch + (size_t) ci); }
 };
 
-struct AConvSrcPlanes {
-  const AConvPlanes &pl;
-  GSTAMD_AC const uint8_t *at (const AConvPlan &, int bytes, size_t n, int ci) const { return pl.p[ci] + (size_t) bytes * n; }
+template <class PL> struct AConvSrcPlanesOf {
+  const PL &pl;
+  GSTAMD_AC const uint8_t *at (const AConvPlan &, int bytes, size_t n, int ci) const { return aconv_plane_ptr (pl, ci) + (size_t) bytes * n; }
 };
+typedef AConvSrcPlanesOf<AConvPlanes> AConvSrcPlanes;
 
 // ---- stage 1: input frame n, output channel co -> one sample in the mid_in format (the mid buffers are interleaved frames) --------------
 template <int K, class Src> GSTAMD_AC void aconv_pre_sample_at (const AConvPlan &p, const Src &src, uint8_t *mid, size_t n, int co)
@@ -914,9 +948,12 @@ template <class PL> GSTAMD_AC AConvSplit aconv_plane_split_of (const PL &pl, int
   if (pl.realign) {                     /* (frames >= 12: aconv_planes_heads) */
     s.head = 4;
     s.groups = (pl.frames - 8) / 4;
-  } else if (pl.head[y] < 4 && pl.frames >= (size_t) pl.head[y] + 4) {
-    s.head = pl.head[y];
-    s.groups = (pl.frames - s.head) / 4;
+  } else {
+    const int head = aconv_plane_head (pl, y);
+    if (head < 4 && pl.frames >= (size_t) head + 4) {
+      s.head = (size_t) head;
+      s.groups = (pl.frames - s.head) / 4;
+    }
   }
   return s;
 }
@@ -926,7 +963,7 @@ GSTAMD_AC AConvSplit aconv_plane_split (const AConvPlanes &pl, int y) { return a
 // the first kernel: lane t of output channel co.  The mixer's sums run over the input planes in ascending order as in aconv_pre_sample_at;
 // a four-frame lane reads B dwords of every plane it uses - aligned ones where all planes reach a dword boundary at the same frame
 // (aconv_planes_heads), B + 1 around its frames otherwise (ANY)
-template <int K, bool ANY> GSTAMD_AC void aconv_pre_group_planes (const AConvPlan &p, const AConvPlanes &src, uint8_t *mid, int co, size_t n)
+template <int K, bool ANY, class PL> GSTAMD_AC void aconv_pre_group_planes (const AConvPlan &p, const PL &src, uint8_t *mid, int co, size_t n)
 {
   constexpr int B = akind_bytes (K);
   const size_t och = (size_t) p.out_ch;
@@ -937,7 +974,7 @@ template <int K, bool ANY> GSTAMD_AC void aconv_pre_group_planes (const AConvPla
     for (int ci = 0; ci < p.in_ch; ci++) {
       if (!((use >> ci) & 1u))
         continue;
-      aconv_unpack4_s32<K, ANY> (p, src.p[ci] + (size_t) B * n, r);
+      aconv_unpack4_s32<K, ANY> (p, aconv_plane_ptr (src, ci) + (size_t) B * n, r);
       for (int j = 0; j < 4; j++)
         res[j] += (int64_t) r[j] * (int64_t) p.mi[ci][co];
     }
@@ -951,7 +988,7 @@ template <int K, bool ANY> GSTAMD_AC void aconv_pre_group_planes (const AConvPla
   for (int ci = 0; ci < p.in_ch; ci++) {
     if (!((use >> ci) & 1u))
       continue;
-    aconv_unpack4_f64<K, ANY> (p, src.p[ci] + (size_t) B * n, r);
+    aconv_unpack4_f64<K, ANY> (p, aconv_plane_ptr (src, ci) + (size_t) B * n, r);
     for (int j = 0; j < 4; j++)
       acc[j] += r[j] * p.m[ci][co];
   }
@@ -961,19 +998,24 @@ template <int K, bool ANY> GSTAMD_AC void aconv_pre_group_planes (const AConvPla
   }
 }
 
-template <int K> GSTAMD_AC void aconv_pre_lane_planes (const AConvPlan &p, const AConvPlanes &src, uint8_t *mid, int co, size_t t)
+template <int K, class PL> GSTAMD_AC void aconv_pre_lane_planes_of (const AConvPlan &p, const PL &src, uint8_t *mid, int co, size_t t)
 {
-  const AConvSplit s = aconv_plane_split (src, co);
+  const AConvSplit s = aconv_plane_split_of (src, co);
   if (t >= aconv_split_lanes (s))
     return;
   if (t >= s.groups) {
-    aconv_pre_sample_at<K> (p, AConvSrcPlanes { src }, mid, aconv_split_single (s, t), co);
+    aconv_pre_sample_at<K> (p, AConvSrcPlanesOf<PL> { src }, mid, aconv_split_single (s, t), co);
     return;
   }
   if (src.realign)
     aconv_pre_group_planes<K, true> (p, src, mid, co, s.head + 4 * t);
   else
     aconv_pre_group_planes<K, false> (p, src, mid, co, s.head + 4 * t);
+}
+
+template <int K> GSTAMD_AC void aconv_pre_lane_planes (const AConvPlan &p, const AConvPlanes &src, uint8_t *mid, int co, size_t t)
+{
+  aconv_pre_lane_planes_of<K> (p, src, mid, co, t);
 }
 
 // the second kernel: lane t of output plane c (PL: AConvPlanes or AConvPlanesWide)
@@ -987,11 +1029,11 @@ template <int K, class PL> GSTAMD_AC void aconv_post_lane_planes_of (const AConv
   const size_t och = (size_t) p.out_ch, q0 = (size_t) c * dst.frames;
   if (t >= s.groups) {
     const size_t n = aconv_split_single (s, t);
-    aconv_post_sample_at<K> (p, jump, ds, mid, n * och + (size_t) c, dst.p[c] + (size_t) B * n, qv, qd, q0 + n);
+    aconv_post_sample_at<K> (p, jump, ds, mid, n * och + (size_t) c, aconv_plane_ptr (dst, c) + (size_t) B * n, qv, qd, q0 + n);
     return;
   }
   const size_t n = s.head + 4 * t;
-  uint8_t *q = dst.p[c] + (size_t) B * n;
+  uint8_t *q = aconv_plane_ptr (dst, c) + (size_t) B * n;
   if (p.mid_out == AMID_F64) {
     double v[4];
     for (int j = 0; j < 4; j++)
@@ -1039,7 +1081,7 @@ template <int K> GSTAMD_AC void aconv_post_lane_planes (const AConvPlan &p, cons
 template <int K, class PL> GSTAMD_AC void aconv_shape_planes_of (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, const PL &dst)
 {
   for (int c = 0; c < p.out_ch; c++)
-    aconv_shape_channel<K> (p, v + (size_t) c * dst.frames, d + (size_t) c * dst.frames, hist, dst.p[c], dst.frames, 0);
+    aconv_shape_channel<K> (p, v + (size_t) c * dst.frames, d + (size_t) c * dst.frames, hist, aconv_plane_ptr (dst, c), dst.frames, 0);
 }
 
 template <int K> GSTAMD_AC void aconv_shape_planes (const AConvPlan &p, const int32_t *v, const int32_t *d, int32_t *hist, const AConvPlanes &dst)
@@ -1166,14 +1208,14 @@ template <int K> GSTAMD_AC void aconv_wide_stage4 (const AConvPlan &p, const uin
 // phase 1: the tile's frames n0 .. n0 + nf - 1 into x.  in_planar: src.p[ci] are the planes, otherwise src.p[0] holds interleaved frames.
 // A run - the tile's samples of a plane, or all of them for interleaved frames - is split like a launch of the unmixed kernels: single
 // samples up to the first dword a sample starts on, lanes of four samples on aligned dwords, single ones again.
-template <int K> GSTAMD_AC void aconv_wide_stage_lane (const AConvPlan &p, const AConvPlanesWide &src, int in_planar, size_t n0, int nf, uint8_t *x, int tid, int nthreads)
+template <int K, class PL> GSTAMD_AC void aconv_wide_stage_lane (const AConvPlan &p, const PL &src, int in_planar, size_t n0, int nf, uint8_t *x, int tid, int nthreads)
 {
   constexpr int B = akind_bytes (K);
   const size_t xs = (size_t) aconv_wide_x_stride (p), ich = (size_t) p.in_ch;
   const size_t runs = in_planar ? ich : 1, count = in_planar ? (size_t) nf : (size_t) nf * ich;
   for (size_t t = (size_t) tid; t < runs * count; t += (size_t) nthreads) {
     const size_t b = t / count, k = t % count;
-    const uint8_t *base = in_planar ? src.p[b] + (size_t) B * n0 : src.p[0] + (size_t) B * n0 * ich;
+    const uint8_t *base = in_planar ? aconv_plane_ptr (src, (int) b) + (size_t) B * n0 : aconv_plane_ptr (src, 0) + (size_t) B * n0 * ich;
     const AConvSplit s = aconv_wide_split (base, B, count);
     if (k >= aconv_split_lanes (s))
       continue;
@@ -1402,6 +1444,77 @@ template <int K> GSTAMD_AC void aconv_shape_many_lane (const AConvPlan &p, const
 {
   if (c < p.out_ch && m.frames)
     aconv_shape_channel<K> (p, m.q, m.q + m.frames * (size_t) p.out_ch, m.hist, m.out, m.frames, c);
+}
+
+// ---- the same for converters with a non-interleaved side and for wide ones ----------------------------------------------
+// gstamd_audio_converter_samples_many takes what gstamd_audio_converter_samples takes: a non-interleaved side is ONE pointer with the planes
+// frames * bytes apart.  So a side is 16 bytes whatever its channel count, and the lane bodies of a non-interleaved side run on an
+// AConvPlanesEven made from it in registers; the 88 and 592 bytes of AConvPlanes / AConvPlanesWide would not fit 64 times.
+struct AConvManySide {          // 16 bytes
+  uint8_t *base;
+  uint32_t frames;              // fewer than 2^30
+  uint32_t how;                 // bits 0 .. 2: AConvPlanesEven::how; bit 3: realign
+};
+
+GSTAMD_AC AConvPlanesEven aconv_many_side (const AConvManySide &e, int bytes)
+{
+  return { e.base, (size_t) e.frames, bytes, (int) (e.how & 7u), (int) ((e.how >> 3) & 1u) };
+}
+
+struct AConvManyPrePlanes {     // 24 bytes: k_aconv_pre_planes_many, k_aconv_wide_mix_many (which looks at no head)
+  AConvManySide in;
+  uint8_t *mid;
+};
+
+struct AConvManyPostPlanes {    // 48 bytes
+  const uint8_t *mid;
+  int32_t *q;                   // with noise shaping: frames * out_ch S32 samples in the quantizer's order, then as many dither words
+  AConvManySide out;            // frames == 0: the resampler only took history - no lanes, no draws
+  AConvDitherState ds;
+  int pad;
+};
+
+struct AConvManyPrePlanesTable { AConvManyPrePlanes s[GSTAMD_ACONV_MANY_MAX]; };
+struct AConvManyPostPlanesTable { AConvManyPostPlanes s[GSTAMD_ACONV_MANY_MAX]; };
+static_assert (sizeof (AConvManySide) == 16 && sizeof (AConvManyPrePlanes) == 24 && sizeof (AConvManyPostPlanes) == 48, "entries of the tables");
+static_assert (sizeof (AConvPlan) + sizeof (void *) + sizeof (AConvManyPostPlanesTable) <= 3840, "kernel arguments end at 4 KB");
+static_assert (sizeof (AConvPlan) + sizeof (AConvWideMatrix) + sizeof (AConvManyPrePlanesTable) + 2 * sizeof (int) <= 3840, "kernel arguments end at 4 KB");
+
+// lane t of row co (an output channel) of stream m: the lane of the stream's own k_aconv_pre_planes / k_aconv_pre_mix launch
+template <int K> GSTAMD_AC void aconv_pre_planes_many_lane (const AConvPlan &p, const AConvManyPrePlanes &m, int co, size_t t)
+{
+  aconv_pre_lane_planes_of<K> (p, aconv_many_side (m.in, akind_bytes (K)), m.mid, co, t);
+}
+
+template <int K> GSTAMD_AC void aconv_pre_mix_many_lane (const AConvPlan &p, const AConvManyPre &m, int co, size_t t)
+{
+  aconv_pre_lane_mix<K> (p, m.in, m.mid, aconv_split_unpack (m.split), co, t);          /* m.split: of the stream's FRAMES */
+}
+
+// lane t of output plane c of stream m: k_aconv_post_planes / k_aconv_wide_post_planes
+template <int K> GSTAMD_AC void aconv_post_planes_many_lane (const AConvPlan &p, const AConvJump &jump, const AConvManyPostPlanes &m, int c, size_t t)
+{
+  const size_t n = (size_t) m.out.frames * (size_t) p.out_ch;
+  aconv_post_lane_planes_of<K> (p, jump, m.ds, m.mid, aconv_many_side (m.out, akind_bytes (K)), m.q, m.q ? m.q + n : nullptr, c, t);
+}
+
+// stream m's one recurrence over plane 0, plane 1, ... (k_aconv_shape_planes / k_aconv_wide_shape_planes); the caller gives every lane
+// of a wave another stream
+template <int K> GSTAMD_AC void aconv_shape_planes_many_lane (const AConvPlan &p, const AConvManyShape &m)
+{
+  if (m.frames && m.q)
+    aconv_shape_planes_of<K> (p, m.q, m.q + m.frames * (size_t) p.out_ch, m.hist, AConvPlanesEven { m.out, m.frames, akind_bytes (K), 4, 0 });
+}
+
+// the workgroup of k_aconv_wide_mix_many for tile `tile_index` of stream m; false: the stream has no such tile and the workgroup leaves
+// (as a whole, before the barrier).  n0 / nf: the tile's first frame and its frames.
+GSTAMD_AC bool aconv_wide_many_tile (const AConvManyPrePlanes &m, size_t tile_index, int tile, size_t *n0, int *nf)
+{
+  *n0 = tile_index * (size_t) tile;
+  if (*n0 >= (size_t) m.in.frames)
+    return false;
+  *nf = (size_t) m.in.frames - *n0 < (size_t) tile ? (int) ((size_t) m.in.frames - *n0) : tile;
+  return true;
 }
 
 #ifndef __HIPCC__

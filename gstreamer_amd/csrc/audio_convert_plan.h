@@ -462,11 +462,31 @@ struct AConvManyItem {
   bool resampler;               // a resampler sits between the two kernels
   bool has_input;               // in[i] != NULL
   size_t in_frames, out_frames;
+  // DESIGN 3.8.5; all zero in a caller that serves the ordinary converters only
+  bool layouts;                 // the caller has the batched kernels for non-interleaved and wide converters too
+  bool passthrough;
+  bool wide;
+  int in_layout, out_layout;
+  const AConvWidePlan *wide_plan;       // of a wide converter: its matrices, which *plan does not hold
 };
 
 inline bool aconv_many_batchable (const AConvManyItem &a)
 {
-  return a.ordinary && !a.plan->endian_swap && a.has_input && a.in_frames > 0 && a.in_frames < ((size_t) 1 << 30) && a.out_frames < ((size_t) 1 << 30);
+  return (a.ordinary || (a.layouts && !a.passthrough)) && !a.plan->endian_swap && a.has_input && a.in_frames > 0 && a.in_frames < ((size_t) 1 << 30) &&
+      a.out_frames < ((size_t) 1 << 30);
+}
+
+// what two converters of a run share beside the bytes of their AConvPlan, which do not tell a non-interleaved from an interleaved mono
+// output (q_stride is 1 in both) and hold no matrix of a wide converter
+inline bool aconv_many_same_shape (const AConvManyItem &a, const AConvManyItem &b)
+{
+  if (a.in_layout != b.in_layout || a.out_layout != b.out_layout || a.wide != b.wide)
+    return false;
+  if (!a.wide)
+    return true;
+  const AConvWidePlan *x = a.wide_plan, *y = b.wide_plan;
+  auto same = [](const auto &u, const auto &v) { return u.size () == v.size () && (u.empty () || memcmp (u.data (), v.data (), u.size () * sizeof (u[0])) == 0); };
+  return x && y && same (x->m, y->m) && same (x->mi, y->mi) && same (x->use, y->use);
 }
 
 // The run that starts at it[0]: how many consecutive streams (at most GSTAMD_ACONV_MANY_MAX) one set of launches serves.  1: it[0] goes
@@ -481,7 +501,7 @@ inline int aconv_many_run_length (const AConvManyItem *it, int n)
   while (run < n && run < GSTAMD_ACONV_MANY_MAX) {
     const AConvManyItem &a = it[run];
     /* (an AConvPlan is zero-filled before it is made and has no padding: equal bytes are equal fields, matrices included) */
-    if (!aconv_many_batchable (a) || a.resampler != it[0].resampler || memcmp (a.plan, it[0].plan, sizeof (AConvPlan)) != 0)
+    if (!aconv_many_batchable (a) || a.resampler != it[0].resampler || memcmp (a.plan, it[0].plan, sizeof (AConvPlan)) != 0 || !aconv_many_same_shape (a, it[0]))
       break;
     bool dup = false;
     for (int k = 0; k < run; k++)
@@ -510,5 +530,83 @@ inline size_t aconv_many_post_entry (const AConvPlan &p, const AConvDitherState 
 }
 
 inline bool aconv_plan_shapes (const AConvPlan &p) { return p.ns && p.quant_shift > 0; }
+
+// ---- which batched kernel a stage of a run is, and the entries of a stream with a non-interleaved side ----------------------
+// aconv_run's own choice of its first kernel, from what a run shares
+enum AConvManyFirst : int { ACONV_FIRST_PLAIN = 0, ACONV_FIRST_PLANES, ACONV_FIRST_MIX, ACONV_FIRST_WIDE };
+
+inline int aconv_many_first (const AConvPlan &p, bool wide, int in_layout, int out_layout)
+{
+  if (wide && (in_layout || p.mix))
+    return ACONV_FIRST_WIDE;
+  if (in_layout)
+    return ACONV_FIRST_PLANES;
+  return out_layout && aconv_pre_grouped_mix (p) ? ACONV_FIRST_MIX : ACONV_FIRST_PLAIN;
+}
+
+// A side of `planes` planes at base, frames * bytes apart, for a launch whose rows are the planes themselves (rows_are_planes: each row
+// takes the head of its own plane, on the device) or read all of them (one head where the planes reach a dword at the same frame,
+// otherwise realign or a lane per frame): aconv_planes_heads for any channel count, in four bits.
+inline AConvManySide aconv_many_side_entry (const uint8_t *base, size_t frames, int planes, int bytes, bool grouped, bool rows_are_planes)
+{
+  AConvManySide e = { (uint8_t *) base, (uint32_t) frames, 4u };
+  if (!grouped)
+    return e;
+  if (rows_are_planes) {
+    e.how = AConvPlanesEven::OWN;
+    return e;
+  }
+  bool same = true;
+  int h0 = 4;
+  for (int c = 0; c < planes; c++) {
+    const int h = aconv_head_at (base + (size_t) c * frames * (size_t) bytes, bytes, frames);
+    h0 = c == 0 ? h : h0;
+    same = same && h == h0;
+  }
+  e.how = same ? (uint32_t) h0 : 4u | (bytes < 4 && frames >= 12 ? 8u : 0u);
+  return e;
+}
+
+// lanes of the longest row
+inline size_t aconv_many_side_lanes (const AConvManySide &e, int bytes, int rows)
+{
+  const AConvPlanesEven pl = aconv_many_side (e, bytes);
+  size_t m = 0;
+  for (int y = 0; y < rows; y++) {
+    const size_t l = aconv_split_lanes (aconv_plane_split_of (pl, y));
+    m = l > m ? l : m;
+  }
+  return m;
+}
+
+inline size_t aconv_many_pre_planes_entry (const AConvPlan &p, const uint8_t *in, size_t in_frames, uint8_t *mid, AConvManyPrePlanes *e)
+{
+  const int b = afmt_bytes (p.in_fmt);
+  *e = { aconv_many_side_entry (in, in_frames, p.in_ch, b, aconv_pre_grouped_planes (p), !p.mix), mid };
+  return aconv_many_side_lanes (e->in, b, p.out_ch);
+}
+
+// interleaved frames into a converter whose layout changes: the split is of the FRAMES (aconv_pre_lane_mix)
+inline size_t aconv_many_pre_mix_entry (const AConvPlan &p, const uint8_t *in, size_t in_frames, uint8_t *mid, AConvManyPre *e)
+{
+  const AConvSplit s = aconv_split (in, afmt_bytes (p.in_fmt) * p.in_ch, in_frames, true);
+  *e = { in, mid, aconv_split_pack (s) };
+  return aconv_split_lanes (s);
+}
+
+// the wide mixing kernel stages every run of samples by itself: no head.  Returns the stream's tiles.
+inline size_t aconv_many_wide_entry (const uint8_t *in, size_t in_frames, uint8_t *mid, int tile, AConvManyPrePlanes *e)
+{
+  *e = { { (uint8_t *) in, (uint32_t) in_frames, 4u }, mid };
+  return (in_frames + (size_t) tile - 1) / (size_t) tile;
+}
+
+inline size_t aconv_many_post_planes_entry (const AConvPlan &p, const AConvDitherState &ds, const uint8_t *mid, uint8_t *out, size_t out_frames, int32_t *q,
+    AConvManyPostPlanes *e)
+{
+  const int b = afmt_bytes (p.out_fmt);
+  *e = { mid, q, aconv_many_side_entry (out, out_frames, p.out_ch, b, aconv_post_grouped (p), true), ds, 0 };
+  return aconv_many_side_lanes (e->out, b, p.out_ch);
+}
 
 }  // namespace gstamd

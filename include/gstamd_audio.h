@@ -211,10 +211,11 @@ int gstamd_audio_converter_get_mix_matrix (GstAmdAudioConverter *convert, float 
  * in[i] / out[i] are what gstamd_audio_converter_samples takes for converters[i]; in == NULL or in[i] == NULL feeds silence;
  * in_frames[i] == 0 skips that stream.  Everything is validated before anything is launched: a NULL converter, a NULL out[i] with
  * out_frames[i] > 0, a NULL input or in_frames[i] != out_frames[i] for a converter without a resampler return GSTAMD_ERR_INVALID with
- * nothing done.  Consecutive converters (up to 64) made with equal arguments - interleaved on both sides, 8 channels or fewer, not a
- * passthrough or a byte swap, non-NULL input, fewer than 2^30 frames - share one first kernel, one gstamd_audio_resampler_resample_many,
- * one second kernel and one noise shaping kernel; every other one, and the same converter a second time, goes through
- * the single-stream path in its place in the order.  The buffers of different streams must not overlap. */
+ * nothing done.  Consecutive converters (up to 64) made with equal arguments - any constructor, layouts and channel count, the mix
+ * matrix of a wide converter included; not a passthrough or a byte swap, non-NULL input, fewer than 2^30 frames - share one first
+ * kernel, one gstamd_audio_resampler_resample_many, one second kernel and one noise shaping kernel; every other
+ * one, and the same converter a second time, goes through the single-stream path in its place in the order.  The buffers of different
+ * streams must not overlap. */
 int gstamd_audio_converter_samples_many (int n, GstAmdAudioConverter *const *converters, int flags, const void *const *in,
     const size_t *in_frames, void *const *out, const size_t *out_frames, void *stream);
 /* for tests: what the calling thread's last gstamd_audio_converter_samples_many did - { batched runs, streams served by batched runs,

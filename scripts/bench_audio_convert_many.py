@@ -1,6 +1,8 @@
-"""Time of one round of 64 audio conversions, one by one and through gstamd_audio_converter_samples_many (DESIGN 3.8.4):
+"""Time of one round of 64 audio conversions, one by one and through gstamd_audio_converter_samples_many (DESIGN 3.8.4, 3.8.5):
 
-  python scripts/bench_audio_convert_many.py [--parent-lib PATH/libgstamddsp.so]        # prints one JSON line per case and library
+  python scripts/bench_audio_convert_many.py [--layouts] [--parent-lib PATH/libgstamddsp.so]    # prints one JSON line per case and library
+
+--layouts: the cases of DESIGN 3.8.5 (non-interleaved sides, the wide converter) instead of those of 3.8.4.
 
 A round is one buffer for each of 64 stereo converters of one plan.  Per plan it is timed as 64 gstamd_audio_converter_samples calls ("loop")
 and as one gstamd_audio_converter_samples_many call ("many"); with --parent-lib the loop is also timed on that library (a build of the commit
@@ -20,21 +22,36 @@ CASES = (("F32LE->S16LE tpdf", 1024, 48000, dict(dither_method="tpdf")),
          ("F32LE->S16LE tpdf high", 1024, 48000, dict(dither_method="tpdf", noise_shaping="high")),
          ("F32LE 48000->S16LE 44100 tpdf kaiser", 1024, 44100, dict(dither_method="tpdf", resampler_method="kaiser")),
          ("F32LE->S16LE tpdf", 48000, 48000, dict(dither_method="tpdf")))
+# (name, frames, out_rate, config, in_layout, out_layout, (in_ch, out_ch) of a wide converter or None)
+LAYOUT_CASES = (("F32LE planar->S16LE tpdf", 1024, 48000, dict(dither_method="tpdf"), 1, 0, None),
+                ("F32LE planar->S16LE planar tpdf high", 1024, 48000, dict(dither_method="tpdf", noise_shaping="high"), 1, 1, None),
+                ("F32LE planar 48000->S16LE planar 44100 tpdf kaiser", 1024, 44100, dict(dither_method="tpdf", resampler_method="kaiser"), 1, 1, None),
+                ("wide F32LE 16ch->S16LE 6ch planar tpdf", 1024, 48000, dict(dither_method="tpdf"), 0, 1, (16, 6)),
+                ("F32LE planar->S16LE tpdf", 48000, 48000, dict(dither_method="tpdf"), 1, 0, None))
 
 
-def measure(label):
+def measure(label, layouts=False):
     import numpy as np
     import torch
     from gstreamer_amd import audio as A
     dev = torch.device("cuda")
     have_many = hasattr(A._conv_lib(), "gstamd_audio_converter_samples_many")
-    for name, frames, out_rate, cfg in CASES:
+    for name, frames, out_rate, cfg, il, ol, wide in (LAYOUT_CASES if layouts else [c + (0, 0, None) for c in CASES]):
         rounds = ROUNDS if frames <= 1024 else 50
-        cvs = [A.AudioConverter(A.audio_info("F32LE", 48000, 2), A.audio_info("S16LE", out_rate, 2), A.audio_converter_config(**cfg)) for _ in range(STREAMS)]
+        in_ch, out_ch = wide or (2, 2)
+        if wide:                                # a dense matrix, the same for all: one run
+            m = np.random.RandomState(2).uniform(-1, 1, (out_ch, in_ch)) / in_ch
+            cvs = [A.AudioConverterWide(A.audio_info_wide("F32LE", 48000, in_ch), A.audio_info_wide("S16LE", out_rate, out_ch), A.audio_converter_config(**cfg),
+                                        in_layout=il, out_layout=ol, mix_matrix=m.tolist()) for _ in range(STREAMS)]
+        elif il or ol:
+            cvs = [A.AudioConverter(A.audio_info("F32LE", 48000, 2), A.audio_info("S16LE", out_rate, 2), A.audio_converter_config(**cfg), in_layout=il, out_layout=ol)
+                   for _ in range(STREAMS)]
+        else:
+            cvs = [A.AudioConverter(A.audio_info("F32LE", 48000, 2), A.audio_info("S16LE", out_rate, 2), A.audio_converter_config(**cfg)) for _ in range(STREAMS)]
         rng = np.random.RandomState(1)
-        src = [torch.from_numpy(rng.uniform(-1, 1, frames * 2).astype(np.float32)).to(dev) for _ in range(STREAMS)]
+        src = [torch.from_numpy(rng.uniform(-1, 1, frames * in_ch).astype(np.float32)).to(dev) for _ in range(STREAMS)]
         # a resampler's output length moves by a frame from buffer to buffer: room for the longest, the frames asked for each round
-        dst = [torch.zeros((frames + 16) * 2, dtype=torch.int16, device=dev) for _ in range(STREAMS)]
+        dst = [torch.zeros((frames + 16) * out_ch, dtype=torch.int16, device=dev) for _ in range(STREAMS)]
         sp, dp = [t.data_ptr() for t in src], [t.data_ptr() for t in dst]
 
         def loop():
@@ -71,7 +88,7 @@ def measure(label):
 
 def main():
     if "--worker" in sys.argv:
-        measure(sys.argv[sys.argv.index("--worker") + 1])
+        measure(sys.argv[sys.argv.index("--worker") + 1], "--layouts" in sys.argv)
         return
     parent = sys.argv[sys.argv.index("--parent-lib") + 1] if "--parent-lib" in sys.argv else None
     # every measurement in a fresh process; with a parent library: parent, this tree, parent, this tree
@@ -80,7 +97,7 @@ def main():
         env.pop("GSTAMD_LIB_PATH", None)
         if lib:
             env["GSTAMD_LIB_PATH"] = os.path.abspath(lib)
-        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--worker", label], env=env)
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--worker", label] + (["--layouts"] if "--layouts" in sys.argv else []), env=env)
 
 
 if __name__ == "__main__":
