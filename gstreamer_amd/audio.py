@@ -44,6 +44,8 @@ def lib():
         L.gstamd_audio_resampler_resample_many.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_void_p),
                                                            C.POINTER(C.c_size_t), C.c_void_p]
         L.gstamd_audio_resampler_debug_get.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int]
+        if hasattr(L, "gstamd_audio_resampler_debug_launches"):    # (absent from an older build loaded as a baseline: resample_debug raises there)
+            L.gstamd_audio_resampler_debug_launches.argtypes = [C.POINTER(C.c_int32), C.c_int]
         L.gstamd_audio_resampler_debug_taps.restype = C.c_long
         L.gstamd_audio_resampler_debug_taps.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_long]
         _ready = True
@@ -88,8 +90,15 @@ class ManyBuffers:
 
 
 def resample_many(resamplers, srcs, in_frames, dsts, out_frames, stream=None):
-    """gstamd_audio_resampler_resample_many: one buffer per resampler, one launch where the resamplers share a filter"""
+    """gstamd_audio_resampler_resample_many: one buffer per resampler, one launch where the resamplers share a filter (full or interpolated mode)"""
     ManyBuffers(resamplers, srcs, in_frames, dsts, out_frames).run(stream)
+
+
+def resample_debug():
+    """what this thread's last resample / resample_planes / resample_many did (gstamd_audio_resampler_debug_launches)"""
+    buf = (C.c_int32 * 4)()
+    lib().gstamd_audio_resampler_debug_launches(buf, 4)
+    return dict(zip(("launches", "interp_lds_launches", "batched", "single"), list(buf)))
 
 
 class AudioResampler:

@@ -285,6 +285,21 @@ GSTAMD_AD void fir_lds_positions (const FirParams &p, long long jb, int nj, int 
   }
 }
 
+// the logical input window under the outputs [jb, jb + nj), deinterleaved: win[c * win_frames + f] = frame lo + f of channel c
+template <typename T>
+GSTAMD_AD void fir_lds_stage_window (const FirParams &p, int win_frames, const T *__restrict__ hist, const T *__restrict__ in, long long jb, int nj,
+    T *win, int tid, int nthreads)
+{
+  long long lo;
+  int span;
+  fir_lds_span (p, jb, nj, &lo, &span);
+  const int C = p.channels;
+  for (int k = tid; k < span * C; k += nthreads) {
+    const int f = k / C, c = k - f * C;          /* interleaved order: neighbouring lanes read neighbouring samples */
+    win[c * win_frames + f] = logical_sample<T> (p, hist, in, lo + f, c);
+  }
+}
+
 // staging, thread tid of nthreads (after fir_lds_positions and a barrier): taps rows of the frames' phases, four taps (one 16-byte
 // piece for float) per step, and the input window
 template <typename T>
@@ -297,14 +312,7 @@ GSTAMD_AD void fir_lds_stage (const FirParams &p, const FirLdsGeom &g, const T *
     const int fr = k / n4, i4 = k - fr * n4;
     *(Q4 *) (rows + fr * g.row_stride + 4 * i4) = *(const Q4 *) (table + (size_t) pos[2 * fr + 1] * p.n_taps_padded + 4 * i4);
   }
-  long long lo;
-  int span;
-  fir_lds_span (p, jb, nj, &lo, &span);
-  const int C = p.channels;
-  for (int k = tid; k < span * C; k += nthreads) {
-    const int f = k / C, c = k - f * C;          /* interleaved order: neighbouring lanes read neighbouring samples */
-    win[c * g.win_frames + f] = logical_sample<T> (p, hist, in, lo + f, c);
-  }
+  fir_lds_stage_window<T> (p, g.win_frames, hist, in, jb, nj, win, tid, nthreads);
 }
 
 // partial sum q of output frame fr of the workgroup, channel c
@@ -335,6 +343,149 @@ GSTAMD_AD T history_sample (const FirParams &p, const T *__restrict__ hist, cons
   if (i < moved)
     return logical_sample<T> (p, hist, in, src_start + i, c);
   return logical_sample<T> (p, hist, in, i, c);
+}
+
+// ------------------------------------------------------------------------------------------------
+// LDS-staged form of the INTERPOLATED inner products (k_fir_interp_lds).  Same geometry as k_fir_lds: a workgroup of 256 lanes owns
+// FIR_LDS_FRAMES consecutive output frames, four lanes a frame.  Staged once per workgroup: the position table, the input window
+// [channel][frame] (fir_lds_stage_window) and the WHOLE oversampled table - oversample + 2 (linear) or + 4 (cubic) rows, every frame
+// reads 2 / 4 neighbouring ones of them - and, per frame, the first row `offset` and the blend weights ic[4] (the divisions of
+// get_taps_<T>_<inter> and make_coeff_<T>_<inter> once per frame, not once per sample-channel).
+// Rows are padded by one bank (row_stride = n_taps_padded + 1 samples of 4 or 8 bytes, + 2 of 2 bytes): n_taps_padded is a multiple
+// of 4, so consecutive rows start an odd number of banks apart and the four rows a quad reads at one tap index are in four banks.
+// The lanes of a quad own the reference's four accumulators (inner_product_<T>_linear_1_c / _cubic_1_c, audio-resampler.c:636-755):
+//   cubic   lane q: r_q = sum over all taps i, ascending, of a[i] * row[offset + q][i]
+//   linear  lane 0: r0 = even i, row offset      lane 1: r1 = even i, row offset + 1
+//           lane 2: r2 = odd i, row offset       lane 3: r3 = odd i, row offset + 1
+// each a * c rounded and then added, in fir_output's order: the bytes are fir_output's.
+// ------------------------------------------------------------------------------------------------
+struct FirInterpGeom {
+  int row_stride;       // samples per staged table row
+  int win_frames;       // staged frames per channel, as FirLdsGeom's
+  int n_rows;           // rows of the oversampled table: oversample + 2 (linear) / + 4 (cubic)
+};
+
+inline int fir_lds_win_frames (int samp_inc, int n_taps_padded)
+{
+  const int span_max = FIR_LDS_FRAMES * (samp_inc + 1) + n_taps_padded + 2;
+  return ((span_max + 31) & ~31) + 16;
+}
+
+// geometry and LDS bytes of an interpolated plan (library and emulator decide with this: the kernel serves the stream when the
+// result is <= FIR_LDS_BUDGET); interp: 1 linear, 2 cubic; bps: bytes per sample
+#define FIR_LDS_BUDGET (64 * 1024)
+inline size_t fir_interp_lds_bytes (int bps, int channels, int n_taps_padded, int samp_inc, int interp, int oversample, FirInterpGeom *g)
+{
+  g->row_stride = n_taps_padded + (bps == 2 ? 2 : 1);
+  g->win_frames = fir_lds_win_frames (samp_inc, n_taps_padded);
+  g->n_rows = oversample + (interp == 2 ? 4 : 2);
+  return ((size_t) g->n_rows * g->row_stride + (size_t) channels * g->win_frames + 4 * FIR_LDS_FRAMES) * (size_t) bps + 2 * FIR_LDS_FRAMES * sizeof (int);
+}
+
+// per frame, by the lane that filled its pos[] entry in fir_lds_positions (same tid / nthreads walk: no barrier in between):
+// pos[2 fr + 1] turns from the phase into the first table row, ic[4 fr ..] are the blend weights
+template <typename T>
+GSTAMD_AD void fir_interp_coeffs (const FirParams &p, int nj, int *pos, T *ic, int tid, int nthreads)
+{
+  for (int fr = tid; fr < nj; fr += nthreads) {
+    const int at = pos[2 * fr + 1] * p.oversample;
+    const int frac = at % p.out_rate;
+    pos[2 * fr + 1] = (p.oversample - 1) - at / p.out_rate;
+    if (p.interp == 1)
+      fir_coeff_linear (frac, p.out_rate, ic + 4 * fr);
+    else
+      fir_coeff_cubic (frac, p.out_rate, ic + 4 * fr);
+  }
+}
+
+// the oversampled table into its padded rows
+template <typename T>
+GSTAMD_AD void fir_interp_stage_table (const FirParams &p, const FirInterpGeom &g, const T *__restrict__ table, T *tab, int tid, int nthreads)
+{
+  const int n = p.n_taps_padded;
+  for (int k = tid; k < g.n_rows * n; k += nthreads) {
+    const int row = k / n, i = k - row * n;
+    tab[row * g.row_stride + i] = table[k];
+  }
+}
+
+// accumulator q of output frame fr of the workgroup, channel c
+template <typename T>
+GSTAMD_AD typename Acc<T>::type fir_interp_partial (const FirParams &p, const FirInterpGeom &g, const int *pos, const T *tab, const T *win, int fr,
+    int q, int c)
+{
+  typedef typename Acc<T>::type A;
+  const T *w = win + c * g.win_frames + pos[2 * fr];
+  A r = 0;
+  if (p.interp == 1) {
+    const T *row = tab + (pos[2 * fr + 1] + (q & 1)) * g.row_stride;
+    for (int i = q >> 1; i < p.n_taps_padded; i += 2)
+      r += (A) w[i] * (A) row[i];
+  } else {
+    const T *row = tab + (pos[2 * fr + 1] + q) * g.row_stride;
+    for (int i = 0; i < p.n_taps_padded; i++)
+      r += (A) w[i] * (A) row[i];
+  }
+  return r;
+}
+
+template <typename T>
+GSTAMD_AD T fir_interp_combine (const FirParams &p, typename Acc<T>::type r0, typename Acc<T>::type r1, typename Acc<T>::type r2,
+    typename Acc<T>::type r3, const T *ic)
+{
+  return p.interp == 1 ? fir_interp_finish_linear<T> (r0, r1, r2, r3, ic) : fir_interp_finish_cubic<T> (r0, r1, r2, r3, ic);
+}
+
+// ---- many streams of one filter in one grid (k_fir_lds_many, k_fir_interp_lds_many): what differs between the streams ----------
+#define GSTAMD_AUDIO_MANY_MAX 64
+struct FirManyStream {
+  const void *hist, *in;
+  void *out, *new_hist;
+  int samp_index0, samp_phase0, hist_frames, in_frames, n_out;
+  int pad;
+};
+struct FirMany {
+  FirManyStream s[GSTAMD_AUDIO_MANY_MAX];
+};
+
+struct FirManyWork {
+  long long src_start, moved, keep;     // the history hand-over of audio_step (audio_taps.cpp), from the same numbers
+  int fir_blocks, hist_blocks;
+};
+
+// stream m's own FirParams from the run's shared ones, and its blocks
+GSTAMD_AD void fir_many_stream (const FirParams &shared, const FirManyStream &m, FirParams *out, FirManyWork *w)
+{
+  FirParams p = shared;
+  p.samp_index0 = m.samp_index0;
+  p.samp_phase0 = m.samp_phase0;
+  p.hist_frames = m.hist_frames;
+  p.total_frames = (long long) m.hist_frames + m.in_frames;
+  p.in_is_null = m.in == nullptr;
+  if (p.in_plane_stride)
+    p.in_plane_stride = m.in_frames;            /* non-interleaved sides: the planes follow each other, as in _resample */
+  if (p.out_plane_stride)
+    p.out_plane_stride = m.n_out;
+  long long src_start = 0, moved = p.total_frames, keep = p.total_frames;
+  if (m.n_out > 0) {
+    const long long tot = (long long) m.samp_phase0 + (long long) m.n_out * p.samp_frac;
+    const long long end_index = (long long) m.samp_index0 + (long long) m.n_out * p.samp_inc + tot / p.out_rate;
+    const long long consumed = end_index - m.samp_index0;
+    if (p.total_frames > end_index) {
+      src_start = end_index;
+      moved = p.total_frames - end_index;
+    } else {
+      src_start = 0;
+      moved = 0;
+    }
+    keep = consumed > 0 ? (p.total_frames - consumed > 0 ? p.total_frames - consumed : 0) : p.total_frames;
+  }
+  w->src_start = src_start;
+  w->moved = moved;
+  w->keep = keep;
+  w->fir_blocks = (int) ((m.n_out + FIR_LDS_FRAMES - 1) / FIR_LDS_FRAMES);
+  w->hist_blocks = keep > 0 ? (int) ((keep * p.channels + 255) / 256) : 0;
+  *out = p;
 }
 
 }  // namespace gstamd

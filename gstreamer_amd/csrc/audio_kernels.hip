@@ -1,6 +1,7 @@
 // audio_kernels.hip - gfx950 kernels + C ABI (include/gstamd_audio.h) of the polyphase FIR resampler.
 //
-// Two kernels per resample() call, both on the caller's stream:
+// One launch per resample() call where the plan fits the LDS budget - k_fir_lds (FULL tables) and k_fir_interp_lds (INTERPOLATED
+// tables) do the FIR and the history hand-over - and otherwise two kernels, both on the caller's stream:
 //   k_fir      one lane per output sample-channel; the phase's taps row (<= a few hundred bytes) and the
 //              input window come through L1/L2 (the whole 147 x 72 f32 table of 48k->44.1k is 42 KB);
 //   k_history  writes the frames the next call still needs into the other history buffer.
@@ -92,53 +93,79 @@ __global__ __launch_bounds__ (256) void k_fir_lds (FirParams p, FirLdsGeom g, co
 // mixer / a multi-channel capture / a transcoding farm go into one grid: blockIdx.y = stream.  What differs between the streams - the
 // buffers and where each stands in its own history - fits 56 bytes, 64 streams fit the kernel arguments; the filter (rates, taps table,
 // channel count, sample type) is the same for all.  Each stream's blocks do exactly what its own k_fir_lds launch would have done.
-#define GSTAMD_AUDIO_MANY_MAX 64
-struct FirManyStream {
-  const void *hist, *in;
-  void *out, *new_hist;
-  int samp_index0, samp_phase0, hist_frames, in_frames, n_out;
-  int pad;
-};
-struct FirMany {
-  FirManyStream s[GSTAMD_AUDIO_MANY_MAX];
-};
-
+// (FirManyStream / FirMany and fir_many_stream, which derives a stream's own numbers, are in audio_device.h.)
 template <typename T>
 __global__ __launch_bounds__ (256) void k_fir_lds_many (FirParams shared, FirLdsGeom g, const T *__restrict__ table, FirMany many)
 {
   const FirManyStream &m = many.s[blockIdx.y];
-  FirParams p = shared;
-  p.samp_index0 = m.samp_index0;
-  p.samp_phase0 = m.samp_phase0;
-  p.hist_frames = m.hist_frames;
-  p.total_frames = (long long) m.hist_frames + m.in_frames;
-  p.in_is_null = m.in == nullptr;
-  if (p.in_plane_stride)
-    p.in_plane_stride = m.in_frames;            /* non-interleaved sides: the planes follow each other, as in _resample */
-  if (p.out_plane_stride)
-    p.out_plane_stride = m.n_out;
-  // the history hand-over of audio_step (audio_taps.cpp), from the same numbers
-  long long src_start = 0, moved = p.total_frames, keep = p.total_frames;
-  if (m.n_out > 0) {
-    const long long tot = (long long) m.samp_phase0 + (long long) m.n_out * p.samp_frac;
-    const long long end_index = (long long) m.samp_index0 + (long long) m.n_out * p.samp_inc + tot / p.out_rate;
-    const long long consumed = end_index - m.samp_index0;
-    if (p.total_frames > end_index) {
-      src_start = end_index;
-      moved = p.total_frames - end_index;
-    } else {
-      src_start = 0;
-      moved = 0;
-    }
-    keep = consumed > 0 ? (p.total_frames - consumed > 0 ? p.total_frames - consumed : 0) : p.total_frames;
-  }
-  const int fir_blocks = (int) ((m.n_out + FIR_LDS_FRAMES - 1) / FIR_LDS_FRAMES);
-  const int hist_blocks = keep > 0 ? (int) ((keep * p.channels + 255) / 256) : 0;
-  if ((int) blockIdx.x >= fir_blocks + hist_blocks)
+  FirParams p;
+  FirManyWork w;
+  fir_many_stream (shared, m, &p, &w);
+  if ((int) blockIdx.x >= w.fir_blocks + w.hist_blocks)
     return;
-  fir_lds_block<T> (p, g, (const T *) m.hist, (const T *) m.in, table, (T *) m.out, m.n_out, fir_blocks, (T *) m.new_hist, src_start, moved, keep,
+  fir_lds_block<T> (p, g, (const T *) m.hist, (const T *) m.in, table, (T *) m.out, m.n_out, w.fir_blocks, (T *) m.new_hist, w.src_start, w.moved, w.keep,
       (int) blockIdx.x);
 }
+
+// INTERPOLATED mode through LDS (audio_device.h, third part): the geometry of fir_lds_block, the whole oversampled table staged instead of
+// one taps row per frame, the lanes of a quad owning the reference's four accumulators.
+template <typename T>
+__device__ __forceinline__ void fir_interp_lds_block (const FirParams &p, const FirInterpGeom &g, const T *__restrict__ hist, const T *__restrict__ in,
+    const T *__restrict__ table, T *__restrict__ out, long long n_out, int fir_blocks, T *__restrict__ new_hist, long long src_start,
+    long long moved, long long keep, int bx)
+{
+  extern __shared__ __attribute__ ((aligned (16))) unsigned char fir_lds_raw[];
+  if (bx >= fir_blocks) {
+    const long long i = (long long) (bx - fir_blocks) * blockDim.x + threadIdx.x;
+    if (i < keep * p.channels)
+      new_hist[i] = history_sample<T> (p, hist, in, src_start, moved, i / p.channels, (int) (i % p.channels));
+    return;
+  }
+  typedef typename Acc<T>::type A;
+  T *tab = (T *) fir_lds_raw, *win = tab + (size_t) g.n_rows * g.row_stride, *ic = win + (size_t) p.channels * g.win_frames;
+  int *pos = (int *) (ic + 4 * FIR_LDS_FRAMES);
+  const long long jb = (long long) bx * FIR_LDS_FRAMES;
+  const int nj = n_out - jb < FIR_LDS_FRAMES ? (int) (n_out - jb) : FIR_LDS_FRAMES;
+  fir_lds_positions (p, jb, nj, pos, (int) threadIdx.x, 256);
+  fir_interp_coeffs<T> (p, nj, pos, ic, (int) threadIdx.x, 256);
+  fir_interp_stage_table<T> (p, g, table, tab, (int) threadIdx.x, 256);
+  fir_lds_stage_window<T> (p, g.win_frames, hist, in, jb, nj, win, (int) threadIdx.x, 256);
+  __syncthreads ();
+  const int fr = (int) threadIdx.x >> 2, q = (int) threadIdx.x & 3;
+  const int frc = fr < nj ? fr : nj - 1;        /* idle quads repeat the last frame (no divergence before the shuffles) */
+  for (int c = 0; c < p.channels; c++) {
+    const A r = fir_interp_partial<T> (p, g, pos, tab, win, frc, q, c);
+    const int lane = (int) (threadIdx.x & 63), base = lane & ~3;
+    const A r0 = __shfl (r, base, 64), r1 = __shfl (r, base + 1, 64), r2 = __shfl (r, base + 2, 64), r3 = __shfl (r, base + 3, 64);
+    if (fr < nj && q == (c & 3))
+      out[fir_out_index (p, jb + fr, c)] = fir_interp_combine<T> (p, r0, r1, r2, r3, ic + 4 * fr);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__ (256) void k_fir_interp_lds (FirParams p, FirInterpGeom g, const T *__restrict__ hist, const T *__restrict__ in,
+    const T *__restrict__ table, T *__restrict__ out, long long n_out, int fir_blocks, T *__restrict__ new_hist, long long src_start,
+    long long moved, long long keep)
+{
+  fir_interp_lds_block<T> (p, g, hist, in, table, out, n_out, fir_blocks, new_hist, src_start, moved, keep, (int) blockIdx.x);
+}
+
+template <typename T>
+__global__ __launch_bounds__ (256) void k_fir_interp_lds_many (FirParams shared, FirInterpGeom g, const T *__restrict__ table, FirMany many)
+{
+  const FirManyStream &m = many.s[blockIdx.y];
+  FirParams p;
+  FirManyWork w;
+  fir_many_stream (shared, m, &p, &w);
+  if ((int) blockIdx.x >= w.fir_blocks + w.hist_blocks)
+    return;
+  fir_interp_lds_block<T> (p, g, (const T *) m.hist, (const T *) m.in, table, (T *) m.out, m.n_out, w.fir_blocks, (T *) m.new_hist, w.src_start, w.moved,
+      w.keep, (int) blockIdx.x);
+}
+
+// what the calling thread's last _resample / _resample_planes / _resample_many did (gstamd_audio_resampler_debug_launches):
+// kernel launches, of those launches of the interpolated LDS kernels, streams served by batched launches, streams gone one by one
+static thread_local int32_t t_launches[4] = {0, 0, 0, 0};
 
 struct GstAmdAudioResampler {
   AudioPlan plan;
@@ -196,6 +223,14 @@ static int ensure_hist (GstAmdAudioResampler *r, int which, size_t frames)
   return GSTAMD_OK;
 }
 
+static unsigned long long hash_table (const std::vector<uint8_t> &table)
+{
+  unsigned long long h = 1469598103934665603ull;
+  for (unsigned char b : table)
+    h = (h ^ b) * 1099511628211ull;
+  return h ^ table.size ();
+}
+
 static int ensure_device (GstAmdAudioResampler *r)
 {
   if (r->device_ready)
@@ -205,10 +240,7 @@ static int ensure_device (GstAmdAudioResampler *r)
       return audio_hip_fail (__func__);
     if (hipMemcpy (r->table_dev, r->plan.table.data (), r->plan.table.size (), hipMemcpyHostToDevice) != hipSuccess)
       return audio_hip_fail (__func__);
-    unsigned long long h = 1469598103934665603ull;
-    for (unsigned char b : r->plan.table)
-      h = (h ^ b) * 1099511628211ull;
-    r->table_hash = h ^ r->plan.table.size ();
+    r->table_hash = hash_table (r->plan.table);
   }
   int e = ensure_hist (r, 0, (size_t) r->plan.n_taps + 64);
   if (e == GSTAMD_OK)
@@ -248,10 +280,33 @@ static int run_resample (GstAmdAudioResampler *r, const void *in, size_t in_fram
 {
   const AudioPlan &pl = r->plan;
   const AudioStep s = audio_step (pl, &r->st, in_frames, out_frames);
+  t_launches[3]++;
   if (s.skipped_all)
     return GSTAMD_OK;
   const FirParams p = make_fir_params (pl, s, in == nullptr, in_stride, out_stride);
   const int cur = r->cur, nxt = cur ^ 1;
+  /* INTERPOLATED mode: one launch of its LDS-staged kernel, when the whole oversampled table fits beside the window */
+  if (s.run_fir && !p.nearest && p.interp && !tuning_on ("GSTAMD_NO_FIR_LDS")) {
+    FirInterpGeom g;
+    const size_t lds = fir_interp_lds_bytes ((int) sizeof (T), pl.channels, p.n_taps_padded, p.samp_inc, p.interp, p.oversample, &g);
+    if (lds <= FIR_LDS_BUDGET) {
+      if (s.keep > 0) {
+        int e = ensure_hist (r, nxt, (size_t) s.keep + 64);
+        if (e != GSTAMD_OK)
+          return e;
+      }
+      const int fir_blocks = (int) ((s.n_out + FIR_LDS_FRAMES - 1) / FIR_LDS_FRAMES);
+      const int hist_blocks = s.keep > 0 ? (int) ((s.keep * pl.channels + 255) / 256) : 0;
+      hipLaunchKernelGGL (k_fir_interp_lds<T>, dim3 ((unsigned) (fir_blocks + hist_blocks)), dim3 (256), lds, stream, p, g, (const T *) r->hist[cur],
+          (const T *) in, (const T *) r->table_dev, (T *) out, s.n_out, fir_blocks, (T *) r->hist[nxt], s.src_start, s.moved, s.keep);
+      if (hipGetLastError () != hipSuccess)
+        return audio_hip_fail (__func__);
+      t_launches[0]++;
+      t_launches[1]++;
+      r->cur = nxt;
+      return GSTAMD_OK;
+    }
+  }
   /* FULL mode: one launch of the LDS-staged kernel does the FIR and the history hand-over */
   if (s.run_fir && !p.nearest && !p.interp && !tuning_on ("GSTAMD_NO_FIR_LDS")) {
     FirLdsGeom g;
@@ -271,6 +326,7 @@ static int run_resample (GstAmdAudioResampler *r, const void *in, size_t in_fram
           (const T *) in, (const T *) r->table_dev, (T *) out, s.n_out, fir_blocks, (T *) r->hist[nxt], s.src_start, s.moved, s.keep);
       if (hipGetLastError () != hipSuccess)
         return audio_hip_fail (__func__);
+      t_launches[0]++;
       r->cur = nxt;
       return GSTAMD_OK;
     }
@@ -281,6 +337,7 @@ static int run_resample (GstAmdAudioResampler *r, const void *in, size_t in_fram
         (const T *) in, (const T *) r->table_dev, (T *) out, s.n_out);
     if (hipGetLastError () != hipSuccess)
       return audio_hip_fail (__func__);
+    t_launches[0]++;
   }
   if (s.keep > 0) {
     int e = ensure_hist (r, nxt, (size_t) s.keep + 64);
@@ -291,6 +348,7 @@ static int run_resample (GstAmdAudioResampler *r, const void *in, size_t in_fram
         (const T *) in, (T *) r->hist[nxt], s.src_start, s.moved, s.keep);
     if (hipGetLastError () != hipSuccess)
       return audio_hip_fail (__func__);
+    t_launches[0]++;
   }
   r->cur = nxt;
   return GSTAMD_OK;
@@ -306,6 +364,7 @@ static int run_many (int n, GstAmdAudioResampler *const *rs, const void *const *
   AudioStep first;
   memset (&first, 0, sizeof (first));
   int max_blocks = 0, live = 0;
+  t_launches[2] += n;
   /* every allocation first, on a COPY of each stream's state: a failure for stream i must not leave streams 0 .. i - 1 advanced (their input consumed,
      r->cur pointing at a history buffer no kernel has written) with nothing launched */
   for (int i = 0; i < n; i++) {
@@ -341,13 +400,23 @@ static int run_many (int n, GstAmdAudioResampler *const *rs, const void *const *
   if (!live || !max_blocks)
     return GSTAMD_OK;
   const FirParams p = make_fir_params (pl, first, false, 1, 1);          /* the per-stream fields are filled in by the kernel */
-  FirLdsGeom g;
-  g.row_stride = p.n_taps_padded + 4;
-  const int span_max = FIR_LDS_FRAMES * (p.samp_inc + 1) + p.n_taps_padded + 2;
-  g.win_frames = ((span_max + 31) & ~31) + 16;
-  const size_t lds = ((size_t) FIR_LDS_FRAMES * g.row_stride + (size_t) pl.channels * g.win_frames) * sizeof (T) + 2 * FIR_LDS_FRAMES * sizeof (int);
-  hipLaunchKernelGGL (k_fir_lds_many<T>, dim3 ((unsigned) max_blocks, (unsigned) live), dim3 (256), lds, stream, p, g, (const T *) rs[0]->table_dev, many);
-  return hipGetLastError () == hipSuccess ? GSTAMD_OK : audio_hip_fail (__func__);
+  if (p.interp) {
+    FirInterpGeom g;
+    const size_t lds = fir_interp_lds_bytes ((int) sizeof (T), pl.channels, p.n_taps_padded, p.samp_inc, p.interp, p.oversample, &g);
+    hipLaunchKernelGGL (k_fir_interp_lds_many<T>, dim3 ((unsigned) max_blocks, (unsigned) live), dim3 (256), lds, stream, p, g, (const T *) rs[0]->table_dev,
+        many);
+    t_launches[1]++;
+  } else {
+    FirLdsGeom g;
+    g.row_stride = p.n_taps_padded + 4;
+    g.win_frames = fir_lds_win_frames (p.samp_inc, p.n_taps_padded);
+    const size_t lds = ((size_t) FIR_LDS_FRAMES * g.row_stride + (size_t) pl.channels * g.win_frames) * sizeof (T) + 2 * FIR_LDS_FRAMES * sizeof (int);
+    hipLaunchKernelGGL (k_fir_lds_many<T>, dim3 ((unsigned) max_blocks, (unsigned) live), dim3 (256), lds, stream, p, g, (const T *) rs[0]->table_dev, many);
+  }
+  if (hipGetLastError () != hipSuccess)
+    return audio_hip_fail (__func__);
+  t_launches[0]++;
+  return GSTAMD_OK;
 }
 
 extern "C" {
@@ -450,6 +519,7 @@ int gstamd_audio_resampler_update (GstAmdAudioResampler *r, int in_rate, int out
       if (hipMemcpy (r->table_dev, r->plan.table.data (), r->plan.table.size (), hipMemcpyHostToDevice) != hipSuccess)
         return audio_hip_fail (__func__);
     }
+    r->table_hash = hash_table (r->plan.table);     /* (what _resample_many compares: of the table now on the device) */
   }
   if (shift.changed) {
     const size_t fbytes = (size_t) r->plan.bps * r->plan.channels;
@@ -503,12 +573,14 @@ int gstamd_audio_resampler_resample (GstAmdAudioResampler *r, const void *in, si
     void *stream)
 {
   /* non-interleaved sides: the planes follow each other, in_frames / out_frames samples apart */
+  memset (t_launches, 0, sizeof (t_launches));
   return resample_strided (r, in, in_frames, out, out_frames, (long long) in_frames, (long long) out_frames, stream);
 }
 
 int gstamd_audio_resampler_resample_planes (GstAmdAudioResampler *r, const void *const in[], size_t in_frames, void *const out[],
     size_t out_frames, void *stream)
 {
+  memset (t_launches, 0, sizeof (t_launches));
   if (!r || (out_frames > 0 && (!out || !out[0])))
     return GSTAMD_ERR_INVALID;
   const AudioPlan &pl = r->plan;
@@ -539,12 +611,14 @@ int gstamd_audio_resampler_resample_planes (GstAmdAudioResampler *r, const void 
 }
 
 /* N independent resamplers, one buffer each, in ONE kernel launch where they share a filter: the same sample type, channel count, layout flags,
- * rates and taps table (resamplers made with the same arguments), full filter mode, at most 2^31 frames of state each.  Results and the
+ * rates, filter mode, interpolation, oversampling and taps table (resamplers made with the same arguments), a plan that fits the LDS budget of its
+ * mode's kernel, at most 2^30 frames a buffer.  Results and the
  * resamplers' states are exactly those of n gstamd_audio_resampler_resample calls (which is also what happens, one by one, for a set that
  * does not qualify).  No reference counterpart: gst_audio_resampler_resample (audio-resampler.c:1750) takes one stream. */
 int gstamd_audio_resampler_resample_many (int n, GstAmdAudioResampler *const *resamplers, const void *const *in, const size_t *in_frames, void *const *out,
     const size_t *out_frames, void *stream)
 {
+  memset (t_launches, 0, sizeof (t_launches));
   if (n < 0 || (n > 0 && (!resamplers || !in_frames || !out || !out_frames)))
     return GSTAMD_ERR_INVALID;
   for (int i = 0; i < n; i++)
@@ -562,8 +636,10 @@ int gstamd_audio_resampler_resample_many (int n, GstAmdAudioResampler *const *re
     if (e != GSTAMD_OK)
       return e;
     const AudioPlan &p0 = r0->plan;
-    const bool full = p0.method != GSTAMD_AUDIO_RESAMPLER_METHOD_NEAREST && p0.in_rate != p0.out_rate && p0.filter_mode != GSTAMD_AUDIO_FILTER_MODE_INTERPOLATED &&
-        !tuning_on ("GSTAMD_NO_FIR_LDS") && !tuning_on ("GSTAMD_NO_FIR_MANY");
+    /* (FULL and INTERPOLATED plans alike: each has its LDS-staged kernel) */
+    const bool full = p0.method != GSTAMD_AUDIO_RESAMPLER_METHOD_NEAREST && p0.in_rate != p0.out_rate && !tuning_on ("GSTAMD_NO_FIR_LDS") &&
+        !tuning_on ("GSTAMD_NO_FIR_MANY");
+    const int interp0 = p0.filter_mode == GSTAMD_AUDIO_FILTER_MODE_INTERPOLATED ? (p0.filter_interpolation == GSTAMD_AUDIO_FILTER_INTERPOLATION_CUBIC ? 2 : 1) : 0;
     int run = 1;
     while (full && done + run < n && run < GSTAMD_AUDIO_MANY_MAX) {
       GstAmdAudioResampler *r = resamplers[done + run];
@@ -581,7 +657,8 @@ int gstamd_audio_resampler_resample_many (int n, GstAmdAudioResampler *const *re
       const AudioPlan &p = r->plan;
       if (p.format != p0.format || p.channels != p0.channels || p.in_rate != p0.in_rate || p.out_rate != p0.out_rate || p.n_taps != p0.n_taps ||
           p.taps_stride != p0.taps_stride || p.in_planar != p0.in_planar || p.out_planar != p0.out_planar || p.method != p0.method ||
-          p.filter_mode != p0.filter_mode || r->table_hash != r0->table_hash)
+          p.filter_mode != p0.filter_mode || p.filter_interpolation != p0.filter_interpolation || p.oversample != p0.oversample ||
+          r->table_hash != r0->table_hash)
         break;
       run++;
     }
@@ -589,7 +666,10 @@ int gstamd_audio_resampler_resample_many (int n, GstAmdAudioResampler *const *re
     /* (a NULL `in` array or a NULL in[i] means silence, as in gstamd_audio_resampler_resample: such sets go one by one - the batched kernel reads in[i]) */
     for (int k = 0; fits && k < run; k++)
       fits = in && in[done + k] && in_frames[done + k] < (1u << 30) && out_frames[done + k] < (1u << 30);
-    if (fits) {
+    if (fits && interp0) {
+      FirInterpGeom g;
+      fits = fir_interp_lds_bytes (p0.bps, p0.channels, p0.taps_stride, p0.samp_inc, interp0, p0.oversample, &g) <= FIR_LDS_BUDGET;
+    } else if (fits) {
       const size_t fbytes = (size_t) p0.bps;
       const size_t lds_need = ((size_t) FIR_LDS_FRAMES * (p0.taps_stride + 4) + (size_t) p0.channels * (((FIR_LDS_FRAMES * (p0.samp_inc + 1) + p0.taps_stride + 2 + 31) & ~31) + 16)) * fbytes +
           2 * FIR_LDS_FRAMES * sizeof (int);
@@ -630,6 +710,13 @@ const char *gstamd_audio_resampler_divergence (GstAmdAudioResampler *r)
     return "";
   std::lock_guard<std::mutex> g (r->lock);
   return r->st.stale_ahead > 0 ? r->divergence.c_str () : "";
+}
+
+int gstamd_audio_resampler_debug_launches (int32_t *out, int max_out)
+{
+  for (int i = 0; out && i < 4 && i < max_out; i++)
+    out[i] = t_launches[i];
+  return 4;
 }
 
 int gstamd_audio_resampler_debug_get (GstAmdAudioResampler *r, int32_t *out, int max_out)

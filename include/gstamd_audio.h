@@ -103,16 +103,20 @@ int gstamd_audio_resampler_resample (GstAmdAudioResampler *resampler, const void
 int gstamd_audio_resampler_resample_planes (GstAmdAudioResampler *resampler, const void *const in[], size_t in_frames,
     void *const out[], size_t out_frames, void *stream);
 
-/* introspection for tests: n_taps, n_phases (reduced out_rate), reduced in_rate, oversample, filter mode */
 /* `n` independent resamplers, one buffer each (in[i] / out[i] interleaved, or non-interleaved planes following each other as in _resample),
- * in ONE kernel launch where they share a filter - resamplers made with the same arguments, full filter mode; up to 64 per launch, longer
- * or mixed sets run as several launches / one by one.  Outputs and resampler states are exactly those of n _resample calls.  For what
+ * in ONE kernel launch where they share a filter - resamplers made with the same arguments, in full or in interpolated filter mode (equal
+ * filter mode, interpolation, oversampling and taps table), whose plan fits the 64 KB of LDS the staged kernels work in; up to 64 per
+ * launch, longer or mixed sets run as several launches / one by one.  Outputs and resampler states are exactly those of n _resample calls.  For what
  * carries many streams at once: the channels of a non-interleaved capture, the inputs of a mixer, a buffer list.  No reference counterpart:
  * gst_audio_resampler_resample (audio-resampler.h:253) takes one stream and the reference has no cross-stream batching. */
 int gstamd_audio_resampler_resample_many (int n, GstAmdAudioResampler *const *resamplers, const void *const *in, const size_t *in_frames,
     void *const *out, const size_t *out_frames, void *stream);
 
+/* introspection for tests: n_taps, n_phases (reduced out_rate), reduced in_rate, oversample, filter mode */
 int gstamd_audio_resampler_debug_get (GstAmdAudioResampler *resampler, int32_t *out, int max_out);
+/* what the calling thread's last _resample, _resample_planes or _resample_many call did, 4 values: kernel launches issued, of those
+ * launches of the interpolated LDS kernels, streams served by batched launches, streams gone one by one.  Returns 4. */
+int gstamd_audio_resampler_debug_launches (int32_t *out, int max_out);
 /* copies the [n_phases][n_taps] taps table (as doubles) out; returns number of values or < 0 */
 long gstamd_audio_resampler_debug_taps (GstAmdAudioResampler *resampler, double *out, long max_out);
 
