@@ -393,3 +393,48 @@ def convert_many_debug():
     buf = (C.c_int32 * 4)()
     _conv_lib().gstamd_audio_converter_debug_many(buf, 4)
     return dict(zip(("runs", "batched", "single", "launches"), list(buf)))
+
+
+# ---- audiomixer (include/gstamd_audio.h) --------------------------------------------------------------------------------------
+class MixerInput(C.Structure):
+    """GstAmdAudioMixerInput: data points at the first frame that lands in the output, at frame out_offset"""
+    _fields_ = [("data", C.c_void_p), ("out_offset", C.c_uint64), ("frames", C.c_uint64), ("volume", C.c_double), ("mute", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+_mix_ready = False
+
+
+def _mix_lib():
+    global _mix_ready
+    L = lib()
+    if not _mix_ready:
+        L.gstamd_audio_mixer_mix.argtypes = [C.c_int, C.c_int, C.POINTER(MixerInput), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.gstamd_audio_mixer_debug_launches.argtypes = [C.POINTER(C.c_int32), C.c_int]
+        _mix_ready = True
+    return L
+
+
+def mixer_input(data, out_offset, frames, volume=1.0, mute=False):
+    """data: a device pointer, a buffer (torch CUDA tensor) or None"""
+    return MixerInput(None if data is None else _ptr(data), out_offset, frames, volume, int(mute), 0)
+
+
+def mixer_inputs(inputs):
+    """the array gstamd_audio_mixer_mix takes, from MixerInput objects (a caller that mixes the same buffers again keeps it)"""
+    return (MixerInput * len(inputs))(*inputs)
+
+
+def mixer_mix(fmt, channels, inputs, out, out_frames, stream=None):
+    """gstamd_audio_mixer_mix: inputs (a list of MixerInput, or a mixer_inputs array) summed in their order into out[0 .. out_frames), one
+    launch per 64 live inputs; fmt: a name of AFMT or a GSTAMD_AFMT_* value.  Asynchronous on `stream`."""
+    arr = inputs if isinstance(inputs, C.Array) else mixer_inputs(inputs)
+    _v._check(_mix_lib().gstamd_audio_mixer_mix(AFMT[fmt] if isinstance(fmt, str) else fmt, channels, arr, len(arr),
+                                                None if out is None else _ptr(out), out_frames, stream))
+
+
+def mixer_debug():
+    """what this thread's last mixer_mix did (gstamd_audio_mixer_debug_launches)"""
+    buf = (C.c_int32 * 4)()
+    _mix_lib().gstamd_audio_mixer_debug_launches(buf, 4)
+    return dict(zip(("launches", "mixed", "skipped"), list(buf)[:3]))

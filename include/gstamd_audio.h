@@ -226,6 +226,38 @@ int gstamd_audio_converter_samples_many (int n, GstAmdAudioConverter *const *con
  * streams gone one by one, launches of the batched converter kernels (the resampler's own not counted) }; returns 4 */
 int gstamd_audio_converter_debug_many (int32_t *out, int max_out);
 
+/* ---- audiomixer (gst-plugins-base/gst/audiomixer: gstaudiomixer.c, gstaudiomixerorc.orc) --------------------------------------------
+ * The sum of many streams of one format into one buffer, as gst_audio_mixer_aggregate_one_buffer builds it pad after pad - here in ONE
+ * launch for up to 64 inputs: every output sample is written once, its running sum kept in registers and taken in array (pad) order,
+ * which the saturating integer adds make observable.  Per sample of an input that is not skipped: volume == 1.0 adds the sample
+ * (audiomixer_orc_add_*); any other volume scales it first (audiomixer_orc_add_volume_*: S16 by (int) (volume * 2048) >> 11, S32 by
+ * (int) (volume * 134217728) >> 27, both saturating; F32 by (float) volume, F64 by volume), with ORC's denormal flush around every
+ * float operation and no fused multiply-add.  NaN payloads are not pinned.  DESIGN 3.9 has the table.
+ * Formats: GSTAMD_AFMT_S16LE, _S32LE, _F32LE, _F64LE, interleaved.  The reference element also mixes S8, U8, U16LE and U32LE: those
+ * return GSTAMD_ERR_UNSUPPORTED here, as does every other GSTAMD_AFMT_* value.  Callers convert first
+ * (gstamd_audio_converter_samples_many) and mix on the same stream; no synchronisation is needed in between. */
+typedef struct GstAmdAudioMixerInput {
+  const void *data;     /* device pointer to the FIRST frame of this input that lands in the output; aligned to the sample size */
+  uint64_t out_offset;  /* output frame at which that first frame lands */
+  uint64_t frames;      /* frames contributed; out_offset + frames <= out_frames */
+  double volume;        /* GstAudioMixerPad "volume", 0 .. 10 */
+  int32_t mute;         /* GstAudioMixerPad "mute" */
+  int32_t reserved;
+} GstAmdAudioMixerInput;
+
+/* out[0 .. out_frames) is written exactly once: frames no input covers are silence (all-zero bytes).  An input is skipped when it is
+ * muted, its volume is below DBL_MIN (the reference's G_MINDOUBLE), it has no frames or data == NULL.  Inputs must not overlap `out`.
+ * Asynchronous on `stream`.  GSTAMD_ERR_INVALID, with nothing launched: n_inputs < 0 (or inputs == NULL with n_inputs > 0), out == NULL
+ * with out_frames > 0, a pointer not aligned to the sample size, out_offset + frames > out_frames, out_frames >= 2^30, channels outside
+ * 1 .. 64, a volume that is NaN, negative or above 10.  Launches: one for up to 64 live inputs (none: one that writes silence); every
+ * further 64 live inputs one more on the same stream, which starts from the output of the one before - the sum is sequential, so the
+ * result is the same. */
+int gstamd_audio_mixer_mix (int format, int channels, const GstAmdAudioMixerInput *inputs, int n_inputs,
+    void *out, size_t out_frames, void *stream);
+/* what the calling thread's last gstamd_audio_mixer_mix did:
+ * { kernel launches, inputs mixed, inputs skipped (mute / volume / empty), 0 }; returns 4 */
+int gstamd_audio_mixer_debug_launches (int32_t *out, int max_out);
+
 #ifdef __cplusplus
 }
 #endif
