@@ -225,6 +225,25 @@ struct GstAmdAudioConverter {
   size_t mid_a_size = 0, mid_b_size = 0;
 };
 
+// what the two constructors share before the plan: how they refuse, and the config they run with
+static GstAmdAudioConverter *aconv_new_fail (int *status, int code, const std::string &msg)
+{
+  aconv_fail (code, msg);
+  if (status)
+    *status = code;
+  return nullptr;
+}
+
+static GstAmdAudioConverterConfig aconv_config_or_default (const GstAmdAudioConverterConfig *config)
+{
+  GstAmdAudioConverterConfig cfg;
+  if (config)
+    cfg = *config;
+  else
+    gstamd_audio_converter_config_init (&cfg);
+  return cfg;
+}
+
 // what the two constructors share once the plan stands: the resampler, the jump table, the error history
 static GstAmdAudioConverter *aconv_finish_new (GstAmdAudioConverter *c, bool resample, int in_rate, int out_rate, int *status)
 {
@@ -288,20 +307,9 @@ GstAmdAudioConverter *gstamd_audio_converter_new (int flags, const GstAmdAudioIn
 GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAmdAudioInfo *in, int in_layout, const GstAmdAudioInfo *out, int out_layout,
     const GstAmdAudioConverterConfig *config, int *status)
 {
-  auto fail = [&](int code, const std::string &msg) -> GstAmdAudioConverter * {
-    if (status)
-      *status = aconv_fail (code, msg);
-    else
-      aconv_fail (code, msg);
-    return nullptr;
-  };
   if (!in || !out)
-    return fail (GSTAMD_ERR_INVALID, "NULL info");
-  GstAmdAudioConverterConfig cfg;
-  if (config)
-    cfg = *config;
-  else
-    gstamd_audio_converter_config_init (&cfg);
+    return aconv_new_fail (status, GSTAMD_ERR_INVALID, "NULL info");
+  const GstAmdAudioConverterConfig cfg = aconv_config_or_default (config);
   GstAmdAudioConverter *c = new GstAmdAudioConverter ();
   c->in = *in;
   c->out = *out;
@@ -314,7 +322,7 @@ GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAm
   const int code = aconv_make_plan_layouts (flags, in, in_layout, out, out_layout, cfg, &c->plan, &resample, &c->passthrough, &err);
   if (code != GSTAMD_OK) {
     delete c;
-    return fail (code, err);
+    return aconv_new_fail (status, code, err);
   }
   return aconv_finish_new (c, resample, in->rate, out->rate, status);
 }
@@ -322,20 +330,9 @@ GstAmdAudioConverter *gstamd_audio_converter_new_layouts (int flags, const GstAm
 GstAmdAudioConverter *gstamd_audio_converter_new_wide (int flags, const GstAmdAudioInfoWide *in, int in_layout, const GstAmdAudioInfoWide *out, int out_layout,
     const GstAmdAudioConverterConfig *config, const float *mix_matrix, int *status)
 {
-  auto fail = [&](int code, const std::string &msg) -> GstAmdAudioConverter * {
-    if (status)
-      *status = aconv_fail (code, msg);
-    else
-      aconv_fail (code, msg);
-    return nullptr;
-  };
   if (!in || !out)
-    return fail (GSTAMD_ERR_INVALID, "NULL info");
-  GstAmdAudioConverterConfig cfg;
-  if (config)
-    cfg = *config;
-  else
-    gstamd_audio_converter_config_init (&cfg);
+    return aconv_new_fail (status, GSTAMD_ERR_INVALID, "NULL info");
+  const GstAmdAudioConverterConfig cfg = aconv_config_or_default (config);
   GstAmdAudioConverter *c = new GstAmdAudioConverter ();
   memset (&c->in, 0, sizeof (c->in));
   memset (&c->out, 0, sizeof (c->out));
@@ -350,7 +347,7 @@ GstAmdAudioConverter *gstamd_audio_converter_new_wide (int flags, const GstAmdAu
   const int code = aconv_make_plan_wide (flags, in, in_layout, out, out_layout, cfg, mix_matrix, &c->wide_plan, &resample, &c->passthrough, &err);
   if (code != GSTAMD_OK) {
     delete c;
-    return fail (code, err);
+    return aconv_new_fail (status, code, err);
   }
   c->plan = c->wide_plan.s;
   /* the matrices: uploaded once, freed in _free */
@@ -366,7 +363,7 @@ GstAmdAudioConverter *gstamd_audio_converter_new_wide (int flags, const GstAmdAu
   c->wide_dev = { m, mi, use };
   if (!up) {
     gstamd_audio_converter_free (c);
-    return fail (GSTAMD_ERR_HIP, "mix matrix upload");
+    return aconv_new_fail (status, GSTAMD_ERR_HIP, "mix matrix upload");
   }
   return aconv_finish_new (c, resample, in->rate, out->rate, status);
 }
@@ -658,216 +655,130 @@ int gstamd_audio_converter_samples (GstAmdAudioConverter *c, int flags, const vo
   return aconv_run (c, in ? ip : nullptr, in_frames, op, out_frames, (hipStream_t) stream);
 }
 
-/* ---- gstamd_audio_converter_samples_many -------------------------------------------------------------------------------- */
+/* ---- gstamd_audio_converter_samples_many: aconv_many_samples of audio_convert_plan.h over this backend ------------------ */
 /* the calling thread's last call: batched runs, streams served by them, streams gone one by one, launches of the batched converter kernels */
 static thread_local int32_t aconv_many_debug[4] = { 0, 0, 0, 0 };
 
-/* a run (aconv_many_run_length) of `run` >= 2 converters of one plan, layout pair and kind: aconv_run's stages, each as one launch over all of them */
-static int aconv_run_many (int run, GstAmdAudioConverter *const *cs, const uint8_t *const *in, const size_t *in_frames, uint8_t *const *out,
-    const size_t *out_frames, hipStream_t stream)
-{
-  const AConvPlan &p = cs[0]->plan;
-  const size_t mid_bytes_in = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
-  const bool shape = aconv_plan_shapes (p), resample = cs[0]->resampler != nullptr;
-  const int out_layout = cs[0]->out_layout;
-  int r;
-  /* every allocation before the first launch */
-  for (int k = 0; k < run; k++) {
-    GstAmdAudioConverter *c = cs[k];
-    if ((r = ensure (&c->mid_a, &c->mid_a_size, in_frames[k] * mid_bytes_in)) != GSTAMD_OK)
+namespace {
+struct AConvManyDevice {
+  GstAmdAudioConverter *const *convs;
+  int flags;
+  hipStream_t stream;
+
+  bool has_convs () const { return convs != nullptr; }
+
+  AConvManyConv conv (int i) const
+  {
+    GstAmdAudioConverter *c = convs[i];
+    if (!c)
+      return {};
+    return { c, &c->plan, c->wide ? &c->wide_plan : nullptr, c->wide, c->passthrough, c->in_layout, c->out_layout, c->resampler, &c->dither, &c->jump_host, c->hist,
+      c->jump_dev, c->wide_dev };
+  }
+
+  int fail (int code, const char *msg) { return aconv_fail (code, msg); }
+
+  int single (const AConvManyConv &c, const void *in, size_t in_frames, void *out, size_t out_frames)
+  {
+    return gstamd_audio_converter_samples ((GstAmdAudioConverter *) c.h, flags, in, in_frames, out, out_frames, stream);
+  }
+
+  int buffers (const AConvManyConv &cv, size_t mid_a_bytes, size_t mid_b_bytes, size_t q_bytes, AConvManyBuffers *b)
+  {
+    GstAmdAudioConverter *c = (GstAmdAudioConverter *) cv.h;
+    int r;
+    if ((r = ensure (&c->mid_a, &c->mid_a_size, mid_a_bytes)) != GSTAMD_OK)
       return r;
-    if (resample && (r = ensure (&c->mid_b, &c->mid_b_size, (out_frames[k] ? out_frames[k] : 1) * mid_bytes_in)) != GSTAMD_OK)
+    if (mid_b_bytes && (r = ensure (&c->mid_b, &c->mid_b_size, mid_b_bytes)) != GSTAMD_OK)
       return r;
     /* the samples and, behind them, the dither words (q_d stays the single-stream path's) */
-    if (shape && out_frames[k] && (r = ensure (&c->q_v, &c->q_v_size, out_frames[k] * (size_t) p.out_ch * 8)) != GSTAMD_OK)
+    if (q_bytes && (r = ensure (&c->q_v, &c->q_v_size, q_bytes)) != GSTAMD_OK)
       return r;
+    *b = { c->mid_a, mid_b_bytes ? c->mid_b : nullptr, q_bytes ? (int32_t *) c->q_v : nullptr };
+    return GSTAMD_OK;
   }
-  switch (aconv_many_first (p, cs[0]->wide, cs[0]->in_layout, out_layout)) {
-    case ACONV_FIRST_WIDE: {
-      AConvManyPrePlanesTable t;
-      memset ((void *) &t, 0, sizeof (t));
-      const int tile = aconv_wide_tile_frames (p.in_ch, p.out_ch);
-      const size_t lds = aconv_wide_lds_bytes (p, tile);        /* of the plan: one value for the launch */
-      size_t tiles = 0;
-      for (int k = 0; k < run; k++) {
-        const size_t l = aconv_many_wide_entry (in[k], in_frames[k], cs[k]->mid_a, tile, &t.s[k]);
-        tiles = l > tiles ? l : tiles;
-      }
-#define PRE(K) k_aconv_wide_mix_many<K><<<dim3 ((unsigned) tiles, (unsigned) run), dim3 (256), lds, stream>>> (p, cs[0]->wide_dev, t, cs[0]->in_layout, tile)
-      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+
+  static unsigned blocks (size_t lanes) { return (unsigned) ((lanes + 255) / 256); }
+
+  void wide_mix (const AConvPlan &p, const AConvWideMatrix &w, const AConvManyPrePlanesTable &t, int in_layout, int tile, size_t tiles, int run)
+  {
+    const size_t lds = aconv_wide_lds_bytes (p, tile);          /* of the plan: one value for the launch */
+#define PRE(K) k_aconv_wide_mix_many<K><<<dim3 ((unsigned) tiles, (unsigned) run), dim3 (256), lds, stream>>> (p, w, t, in_layout, tile)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
 #undef PRE
-      break;
-    }
-    case ACONV_FIRST_PLANES: {
-      AConvManyPrePlanesTable t;
-      memset ((void *) &t, 0, sizeof (t));
-      size_t lanes = 0;
-      for (int k = 0; k < run; k++) {
-        const size_t l = aconv_many_pre_planes_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
-        lanes = l > lanes ? l : lanes;
-      }
-#define PRE(K) k_aconv_pre_planes_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, t)
-      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
-#undef PRE
-      break;
-    }
-    case ACONV_FIRST_MIX: {
-      AConvManyPreTable t;
-      memset ((void *) &t, 0, sizeof (t));
-      size_t lanes = 0;
-      for (int k = 0; k < run; k++) {
-        const size_t l = aconv_many_pre_mix_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
-        lanes = l > lanes ? l : lanes;
-      }
-#define PRE(K) k_aconv_pre_mix_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, t)
-      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
-#undef PRE
-      break;
-    }
-    default: {
-      AConvManyPreTable t;
-      memset ((void *) &t, 0, sizeof (t));
-      size_t lanes = 0;
-      for (int k = 0; k < run; k++) {
-        const size_t l = aconv_many_pre_entry (p, in[k], in_frames[k], cs[k]->mid_a, &t.s[k]);
-        lanes = l > lanes ? l : lanes;
-      }
-#define PRE(K) k_aconv_pre_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, t)
-      GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
-#undef PRE
-      break;
-    }
   }
-  aconv_many_debug[3]++;
-  if (resample) {
+
+  void pre_planes (const AConvPlan &p, const AConvManyPrePlanesTable &t, size_t lanes, int run)
+  {
+#define PRE(K) k_aconv_pre_planes_many<K><<<dim3 (blocks (lanes), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+  }
+
+  void pre_mix (const AConvPlan &p, const AConvManyPreTable &t, size_t lanes, int run)
+  {
+#define PRE(K) k_aconv_pre_mix_many<K><<<dim3 (blocks (lanes), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+  }
+
+  void pre (const AConvPlan &p, const AConvManyPreTable &t, size_t lanes, int run)
+  {
+#define PRE(K) k_aconv_pre_many<K><<<dim3 (blocks (lanes), (unsigned) run), dim3 (256), 0, stream>>> (p, t)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+  }
+
+  void post_planes (const AConvPlan &p, const AConvJump *jump, const AConvManyPostPlanesTable &t, size_t lanes, int run)
+  {
+#define POST(K) k_aconv_post_planes_many<K><<<dim3 (blocks (lanes), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, jump, t)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+  }
+
+  void shape_planes (const AConvPlan &p, const AConvManyShapeTable &sh)
+  {
+#define SHAPE(K) k_aconv_shape_planes_many<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, sh)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+  }
+
+  void post (const AConvPlan &p, const AConvJump *jump, const AConvManyPostTable &t, size_t lanes, int run)
+  {
+#define POST(K) k_aconv_post_many<K><<<dim3 (blocks (lanes), (unsigned) run), dim3 (256), 0, stream>>> (p, jump, t)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+  }
+
+  void shape (const AConvPlan &p, const AConvManyShapeTable &sh, int run)
+  {
+#define SHAPE(K) k_aconv_shape_many<K><<<dim3 ((unsigned) run), dim3 (64), 0, stream>>> (p, sh)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+  }
+
+  int resample_many (int run, const AConvManyConv *cs, const AConvManyBuffers *b, const size_t *in_frames, const size_t *out_frames)
+  {
     GstAmdAudioResampler *rs[GSTAMD_ACONV_MANY_MAX];
     const void *ri[GSTAMD_ACONV_MANY_MAX];
     void *ro[GSTAMD_ACONV_MANY_MAX];
     for (int k = 0; k < run; k++) {
-      rs[k] = cs[k]->resampler;
-      ri[k] = cs[k]->mid_a;
-      ro[k] = cs[k]->mid_b;
+      rs[k] = (GstAmdAudioResampler *) cs[k].resampler;
+      ri[k] = b[k].mid_a;
+      ro[k] = b[k].mid_b;
     }
-    /* one launch where the filter qualifies, per stream where it does not: its own decision */
-    if ((r = gstamd_audio_resampler_resample_many (run, rs, ri, in_frames, ro, out_frames, stream)) != GSTAMD_OK)
-      return r;
+    return gstamd_audio_resampler_resample_many (run, rs, ri, in_frames, ro, out_frames, stream);
   }
-  AConvManyShapeTable sh;
-  memset ((void *) &sh, 0, sizeof (sh));
-  size_t lanes = 0;
-  if (out_layout) {
-    AConvManyPostPlanesTable t;
-    memset ((void *) &t, 0, sizeof (t));
-    for (int k = 0; k < run; k++) {
-      GstAmdAudioConverter *c = cs[k];
-      int32_t *q = shape && out_frames[k] ? (int32_t *) c->q_v : nullptr;
-      const size_t l = aconv_many_post_planes_entry (p, c->dither, resample ? c->mid_b : c->mid_a, out[k], out_frames[k], q, &t.s[k]);
-      lanes = l > lanes ? l : lanes;
-      sh.s[k] = { q, c->hist, out[k], out_frames[k] };
-    }
-    if (lanes) {
-#define POST(K) k_aconv_post_planes_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) p.out_ch, (unsigned) run), dim3 (256), 0, stream>>> (p, \
-    cs[0]->jump_dev, t)
-      GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
-#undef POST
-      aconv_many_debug[3]++;
-      if (shape) {
-#define SHAPE(K) k_aconv_shape_planes_many<K><<<dim3 (1), dim3 (64), 0, stream>>> (p, sh)
-        GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
-#undef SHAPE
-        aconv_many_debug[3]++;
-      }
-    }
-  } else {
-    AConvManyPostTable t;
-    memset ((void *) &t, 0, sizeof (t));
-    for (int k = 0; k < run; k++) {
-      GstAmdAudioConverter *c = cs[k];
-      int32_t *q = shape && out_frames[k] ? (int32_t *) c->q_v : nullptr;
-      const size_t l = aconv_many_post_entry (p, c->dither, resample ? c->mid_b : c->mid_a, out[k], out_frames[k], q, &t.s[k]);
-      lanes = l > lanes ? l : lanes;
-      sh.s[k] = { q, c->hist, out[k], out_frames[k] };
-    }
-    if (lanes) {                                /* 0: every resampler of the run only took input into its history */
-#define POST(K) k_aconv_post_many<K><<<dim3 ((unsigned) ((lanes + 255) / 256), (unsigned) run), dim3 (256), 0, stream>>> (p, cs[0]->jump_dev, t)
-      GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
-#undef POST
-      aconv_many_debug[3]++;
-      if (shape) {
-#define SHAPE(K) k_aconv_shape_many<K><<<dim3 ((unsigned) run), dim3 (64), 0, stream>>> (p, sh)
-        GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
-#undef SHAPE
-        aconv_many_debug[3]++;
-      }
-    }
-  }
-  if (hipGetLastError () != hipSuccess)
-    return aconv_fail (GSTAMD_ERR_HIP, "kernel launch");
-  for (int k = 0; k < run; k++)
-    aconv_dither_advance (p, cs[k]->jump_host, &cs[k]->dither, out_frames[k] * (size_t) p.out_ch);
-  return GSTAMD_OK;
-}
+
+  int launched () { return hipGetLastError () != hipSuccess ? aconv_fail (GSTAMD_ERR_HIP, "kernel launch") : GSTAMD_OK; }
+};
+}  // namespace
 
 int gstamd_audio_converter_samples_many (int n, GstAmdAudioConverter *const *converters, int flags, const void *const *in, const size_t *in_frames,
     void *const *out, const size_t *out_frames, void *stream)
 {
-  memset (aconv_many_debug, 0, sizeof (aconv_many_debug));
-  if (n < 0 || (n > 0 && (!converters || !in_frames || !out_frames)))
-    return aconv_fail (GSTAMD_ERR_INVALID, "NULL argument array");
-  /* everything that can refuse a stream, for all of them, before anything is launched: what gstamd_audio_converter_samples checks */
-  for (int i = 0; i < n; i++) {
-    const GstAmdAudioConverter *c = converters[i];
-    if (!c || (out_frames[i] && (!out || !out[i])))
-      return aconv_fail (GSTAMD_ERR_INVALID, "NULL converter or output");
-    if (in_frames[i] == 0)
-      continue;
-    if (!c->resampler && !(in && in[i]))
-      return aconv_fail (GSTAMD_ERR_INVALID, "NULL input");
-    if (!c->resampler && !c->passthrough && in_frames[i] != out_frames[i])
-      return aconv_fail (GSTAMD_ERR_INVALID, "in_frames != out_frames without a resampler");
-  }
-  std::vector<AConvManyItem> items;
-  std::vector<int> at;                          /* items[j] is stream at[j] of the call: the streams with in_frames == 0 are skipped here */
-  items.reserve ((size_t) n);
-  at.reserve ((size_t) n);
-  for (int i = 0; i < n; i++) {
-    const GstAmdAudioConverter *c = converters[i];
-    if (in_frames[i] == 0)
-      continue;
-    items.push_back ({ &c->plan, c, !c->wide && !c->in_layout && !c->out_layout && !c->passthrough, c->resampler != nullptr, in && in[i] != nullptr,
-        in_frames[i], out_frames[i], true, c->passthrough, c->wide, c->in_layout, c->out_layout, c->wide ? &c->wide_plan : nullptr });
-    at.push_back (i);
-  }
-  const int live = (int) items.size ();
-  for (int done = 0; done < live;) {
-    const int run = aconv_many_run_length (&items[(size_t) done], live - done);
-    int r;
-    if (run < 2) {
-      const int i = at[(size_t) done];
-      r = gstamd_audio_converter_samples (converters[i], flags, in ? in[i] : nullptr, in_frames[i], out ? out[i] : nullptr, out_frames[i], stream);
-      aconv_many_debug[2]++;
-    } else {
-      GstAmdAudioConverter *cs[GSTAMD_ACONV_MANY_MAX];
-      const uint8_t *ip[GSTAMD_ACONV_MANY_MAX];
-      uint8_t *op[GSTAMD_ACONV_MANY_MAX];
-      size_t inf[GSTAMD_ACONV_MANY_MAX], outf[GSTAMD_ACONV_MANY_MAX];
-      for (int k = 0; k < run; k++) {
-        const int i = at[(size_t) (done + k)];
-        cs[k] = converters[i];
-        ip[k] = (const uint8_t *) in[i];
-        op[k] = out ? (uint8_t *) out[i] : nullptr;
-        inf[k] = in_frames[i];
-        outf[k] = out_frames[i];
-      }
-      r = aconv_run_many (run, cs, ip, inf, op, outf, (hipStream_t) stream);
-      aconv_many_debug[0]++;
-      aconv_many_debug[1] += run;
-    }
-    if (r != GSTAMD_OK)
-      return r;
-    done += run;
-  }
-  return GSTAMD_OK;
+  AConvManyDevice be = { converters, flags, (hipStream_t) stream };
+  return aconv_many_samples (be, n, in, in_frames, out, out_frames, aconv_many_debug);
 }
 
 int gstamd_audio_converter_debug_many (int32_t *out, int max_out)

@@ -452,9 +452,13 @@ inline int aconv_make_plan_wide (int flags, const GstAmdAudioInfoWide *in, int i
       (int *) plan->mi.data (), out->channels, plan->use.data (), resample, passthrough, err);
 }
 
-// ---- gstamd_audio_converter_samples_many: which streams of a call share a set of launches --------------------------------
-// One stream of the call as the decision sees it.  Streams with in_frames == 0 are skipped before the walk ("skipping empty buffer"): they
-// do nothing, so they neither belong to a run nor end one.
+// ---- gstamd_audio_converter_samples_many: which streams of a call share a set of launches, the entries of a stream
+// in the tables of the batched kernels, and the call itself as one walk over a backend - the device (audio_convert.hip, whose backend
+// launches the kernels) or the host (tests/emu/emu_audio_many.cpp, whose backend loops over the grid of each launch).  What the two
+// backends do not supply they cannot do differently.
+//
+// One stream of the call as the decision sees it; aconv_many_item makes it.  Streams with in_frames == 0 are skipped before the walk
+// ("skipping empty buffer"): they do nothing, so they neither belong to a run nor end one.
 struct AConvManyItem {
   const AConvPlan *plan;
   const void *id;               // the converter: the same one twice in a run would make its second buffer depend on its first
@@ -462,8 +466,12 @@ struct AConvManyItem {
   bool resampler;               // a resampler sits between the two kernels
   bool has_input;               // in[i] != NULL
   size_t in_frames, out_frames;
-  // DESIGN 3.8.5; all zero in a caller that serves the ordinary converters only
-  bool layouts;                 // the caller has the batched kernels for non-interleaved and wide converters too
+  // A revision's tests, with their emulator sources (tests/emu), are also run against the next revision's library and headers.  Those of
+  // the revision before the one walk (its emu_audio_many.cpp and emu_audio_many_layouts.cpp) fill this struct by position, the former
+  // the seven members above alone: it leaves the rest zero and batches the ordinary converters only.  For them to build and to decide
+  // as they did, `ordinary`, `layouts` and the order of the members stay for now; once no such source is run any more they can go,
+  // and aconv_many_batchable then begins with !a.passthrough.
+  bool layouts;                 // the caller has the batched kernels for non-interleaved and wide converters too: always, in aconv_many_item
   bool passthrough;
   bool wide;
   int in_layout, out_layout;
@@ -513,7 +521,7 @@ inline int aconv_many_run_length (const AConvManyItem *it, int n)
   return run;
 }
 
-// a stream's entries in the tables of the batched kernels; each returns the stream's lanes.  The splits are those of aconv_run's own
+// ---- a stream's entries in the tables of the batched kernels; each returns the stream's lanes.  The splits are those of aconv_run's own
 // launches: computed per stream, since every caller buffer has its own byte phase.
 inline size_t aconv_many_pre_entry (const AConvPlan &p, const uint8_t *in, size_t in_frames, uint8_t *mid, AConvManyPre *e)
 {
@@ -531,7 +539,6 @@ inline size_t aconv_many_post_entry (const AConvPlan &p, const AConvDitherState 
 
 inline bool aconv_plan_shapes (const AConvPlan &p) { return p.ns && p.quant_shift > 0; }
 
-// ---- which batched kernel a stage of a run is, and the entries of a stream with a non-interleaved side ----------------------
 // aconv_run's own choice of its first kernel, from what a run shares
 enum AConvManyFirst : int { ACONV_FIRST_PLAIN = 0, ACONV_FIRST_PLANES, ACONV_FIRST_MIX, ACONV_FIRST_WIDE };
 
@@ -607,6 +614,218 @@ inline size_t aconv_many_post_planes_entry (const AConvPlan &p, const AConvDithe
   const int b = afmt_bytes (p.out_fmt);
   *e = { mid, q, aconv_many_side_entry (out, out_frames, p.out_ch, b, aconv_post_grouped (p), true), ds, 0 };
   return aconv_many_side_lanes (e->out, b, p.out_ch);
+}
+
+// ---- the call ------------------------------------------------------------------------------------------------------------------------
+// What the walk reads of a converter; a backend fills it from its own handle.
+struct AConvManyConv {
+  void *h;                      // the backend's handle, and the converter's identity; NULL: the call has no converter here
+  const AConvPlan *plan;
+  const AConvWidePlan *wide_plan;       // of a wide converter, else NULL
+  bool wide, passthrough;
+  int in_layout, out_layout;
+  void *resampler;              // the backend's own, or NULL
+  AConvDitherState *dither;
+  const AConvJump *jump_host;
+  int32_t *hist;                // where the shape launches find it
+  const AConvJump *jump;        // where the post launches find the table: device memory on the device
+  AConvWideMatrix matrix;       // the same of a wide converter's matrices
+};
+
+// a stream's buffers in a run, where the launches find them
+struct AConvManyBuffers {
+  uint8_t *mid_a, *mid_b;       // before / after the resampler (mid_b: NULL without one)
+  int32_t *q;                   // the samples and, behind them, the dither words of a stream that shapes noise, else NULL
+};
+
+// a stream as aconv_many_run_length sees it: the one place that fills an item, for the library and the emulator alike
+inline AConvManyItem aconv_many_item (const AConvManyConv &c, bool has_input, size_t in_frames, size_t out_frames)
+{
+  return { c.plan, c.h, !c.wide && !c.in_layout && !c.out_layout && !c.passthrough, c.resampler != nullptr, has_input, in_frames, out_frames, true, c.passthrough,
+    c.wide, c.in_layout, c.out_layout, c.wide_plan };
+}
+
+// A backend B supplies
+//   bool has_convs ()                                  the call's array of converters is not NULL
+//   AConvManyConv conv (int i)                         converter i of the call
+//   int fail (int code, const char *msg)               returns code
+//   int single (c, in, in_frames, out, out_frames)     the single-stream call
+//   int buffers (c, mid_a_bytes, mid_b_bytes, q_bytes, AConvManyBuffers *)     0 bytes: not needed, NULL
+//   void pre / pre_planes / pre_mix (p, table, lanes, run), void wide_mix (p, matrix, table, in_layout, tile, tiles, run),
+//   void post / post_planes (p, jump, table, lanes, run), void shape (p, table, run), void shape_planes (p, table)
+//                                                      the batched launches, named after their kernels (k_aconv_<name>_many)
+//   int resample_many (run, cs, buffers, in_frames, out_frames)
+//   int launched ()                                    GSTAMD_OK unless a launch failed; the run needs its buffers no longer
+//
+// A run (aconv_many_run_length) of `run` >= 2 converters of one plan, layout pair and kind: aconv_run's stages, each as one launch over
+// all of them.  record[3] counts the launches of the batched converter kernels.
+template <typename B>
+inline int aconv_many_run (B &be, int run, const AConvManyConv *cs, const uint8_t *const *in, const size_t *in_frames, uint8_t *const *out,
+    const size_t *out_frames, int32_t *record)
+{
+  const AConvPlan &p = *cs[0].plan;
+  const size_t mid_bytes_in = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
+  const bool shape = aconv_plan_shapes (p), resample = cs[0].resampler != nullptr;
+  const int out_layout = cs[0].out_layout;
+  AConvManyBuffers b[GSTAMD_ACONV_MANY_MAX];
+  int r;
+  /* every allocation before the first launch */
+  for (int k = 0; k < run; k++)
+    if ((r = be.buffers (cs[k], in_frames[k] * mid_bytes_in, resample ? (out_frames[k] ? out_frames[k] : 1) * mid_bytes_in : 0,
+             shape && out_frames[k] ? out_frames[k] * (size_t) p.out_ch * 8 : 0, &b[k])) != GSTAMD_OK)
+      return r;
+  size_t lanes = 0;
+  switch (aconv_many_first (p, cs[0].wide, cs[0].in_layout, out_layout)) {
+    case ACONV_FIRST_WIDE: {
+      AConvManyPrePlanesTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      const int tile = aconv_wide_tile_frames (p.in_ch, p.out_ch);
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_wide_entry (in[k], in_frames[k], b[k].mid_a, tile, &t.s[k]);
+        lanes = l > lanes ? l : lanes;          /* tiles, here */
+      }
+      be.wide_mix (p, cs[0].matrix, t, cs[0].in_layout, tile, lanes, run);      /* the matrix is the first converter's: a run shares it */
+      break;
+    }
+    case ACONV_FIRST_PLANES: {
+      AConvManyPrePlanesTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_pre_planes_entry (p, in[k], in_frames[k], b[k].mid_a, &t.s[k]);
+        lanes = l > lanes ? l : lanes;
+      }
+      be.pre_planes (p, t, lanes, run);
+      break;
+    }
+    case ACONV_FIRST_MIX: {
+      AConvManyPreTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_pre_mix_entry (p, in[k], in_frames[k], b[k].mid_a, &t.s[k]);
+        lanes = l > lanes ? l : lanes;
+      }
+      be.pre_mix (p, t, lanes, run);
+      break;
+    }
+    default: {
+      AConvManyPreTable t;
+      memset ((void *) &t, 0, sizeof (t));
+      for (int k = 0; k < run; k++) {
+        const size_t l = aconv_many_pre_entry (p, in[k], in_frames[k], b[k].mid_a, &t.s[k]);
+        lanes = l > lanes ? l : lanes;
+      }
+      be.pre (p, t, lanes, run);
+      break;
+    }
+  }
+  record[3]++;
+  /* one launch where the filter qualifies, per stream where it does not: resample_many's own decision */
+  if (resample && (r = be.resample_many (run, cs, b, in_frames, out_frames)) != GSTAMD_OK)
+    return r;
+  AConvManyShapeTable sh;
+  memset ((void *) &sh, 0, sizeof (sh));
+  lanes = 0;                                    /* stays 0 where every resampler of the run only took input into its history */
+  if (out_layout) {
+    AConvManyPostPlanesTable t;
+    memset ((void *) &t, 0, sizeof (t));
+    for (int k = 0; k < run; k++) {
+      const size_t l = aconv_many_post_planes_entry (p, *cs[k].dither, resample ? b[k].mid_b : b[k].mid_a, out[k], out_frames[k], b[k].q, &t.s[k]);
+      lanes = l > lanes ? l : lanes;
+      sh.s[k] = { b[k].q, cs[k].hist, out[k], out_frames[k] };
+    }
+    if (lanes) {
+      be.post_planes (p, cs[0].jump, t, lanes, run);
+      record[3]++;
+      if (shape) {
+        be.shape_planes (p, sh);
+        record[3]++;
+      }
+    }
+  } else {
+    AConvManyPostTable t;
+    memset ((void *) &t, 0, sizeof (t));
+    for (int k = 0; k < run; k++) {
+      const size_t l = aconv_many_post_entry (p, *cs[k].dither, resample ? b[k].mid_b : b[k].mid_a, out[k], out_frames[k], b[k].q, &t.s[k]);
+      lanes = l > lanes ? l : lanes;
+      sh.s[k] = { b[k].q, cs[k].hist, out[k], out_frames[k] };
+    }
+    if (lanes) {
+      be.post (p, cs[0].jump, t, lanes, run);
+      record[3]++;
+      if (shape) {
+        be.shape (p, sh, run);
+        record[3]++;
+      }
+    }
+  }
+  if ((r = be.launched ()) != GSTAMD_OK)
+    return r;
+  /* the generators move on by the draws of this call */
+  for (int k = 0; k < run; k++)
+    aconv_dither_advance (p, *cs[k].jump_host, cs[k].dither, out_frames[k] * (size_t) p.out_ch);
+  return GSTAMD_OK;
+}
+
+// The whole call.  record: { batched runs, streams served by them, streams gone one by one, launches of the batched converter kernels }.
+template <typename B>
+inline int aconv_many_samples (B &be, int n, const void *const *in, const size_t *in_frames, void *const *out, const size_t *out_frames, int32_t *record)
+{
+  record[0] = record[1] = record[2] = record[3] = 0;
+  if (n < 0 || (n > 0 && (!be.has_convs () || !in_frames || !out_frames)))
+    return be.fail (GSTAMD_ERR_INVALID, "NULL argument array");
+  /* everything that can refuse a stream, for all of them, before anything is launched: what gstamd_audio_converter_samples checks */
+  std::vector<AConvManyConv> cv ((size_t) (n > 0 ? n : 0));       /* the view of every stream's converter, made once */
+  for (int i = 0; i < n; i++) {
+    const AConvManyConv &c = cv[(size_t) i] = be.conv (i);
+    if (!c.h || (out_frames[i] && (!out || !out[i])))
+      return be.fail (GSTAMD_ERR_INVALID, "NULL converter or output");
+    if (in_frames[i] == 0)
+      continue;
+    if (!c.resampler && !(in && in[i]))
+      return be.fail (GSTAMD_ERR_INVALID, "NULL input");
+    if (!c.resampler && !c.passthrough && in_frames[i] != out_frames[i])
+      return be.fail (GSTAMD_ERR_INVALID, "in_frames != out_frames without a resampler");
+  }
+  std::vector<AConvManyItem> items;
+  std::vector<int> at;                          /* items[j] is stream at[j] of the call: the streams with in_frames == 0 are skipped here */
+  items.reserve ((size_t) n);
+  at.reserve ((size_t) n);
+  for (int i = 0; i < n; i++) {
+    if (in_frames[i] == 0)
+      continue;
+    items.push_back (aconv_many_item (cv[(size_t) i], in && in[i] != nullptr, in_frames[i], out_frames[i]));
+    at.push_back (i);
+  }
+  const int live = (int) items.size ();
+  for (int done = 0; done < live;) {
+    const int run = aconv_many_run_length (&items[(size_t) done], live - done);
+    int r;
+    if (run < 2) {
+      const int i = at[(size_t) done];
+      r = be.single (cv[(size_t) i], in ? in[i] : nullptr, in_frames[i], out ? out[i] : nullptr, out_frames[i]);
+      record[2]++;
+    } else {
+      AConvManyConv cs[GSTAMD_ACONV_MANY_MAX];
+      const uint8_t *ip[GSTAMD_ACONV_MANY_MAX];
+      uint8_t *op[GSTAMD_ACONV_MANY_MAX];
+      size_t inf[GSTAMD_ACONV_MANY_MAX], outf[GSTAMD_ACONV_MANY_MAX];
+      for (int k = 0; k < run; k++) {
+        const int i = at[(size_t) (done + k)];
+        cs[k] = cv[(size_t) i];
+        ip[k] = (const uint8_t *) in[i];
+        op[k] = out ? (uint8_t *) out[i] : nullptr;
+        inf[k] = in_frames[i];
+        outf[k] = out_frames[i];
+      }
+      r = aconv_many_run (be, run, cs, ip, inf, op, outf, record);
+      record[0]++;
+      record[1] += run;
+    }
+    if (r != GSTAMD_OK)
+      return r;
+    done += run;
+  }
+  return GSTAMD_OK;
 }
 
 }  // namespace gstamd

@@ -1,18 +1,20 @@
-// tests/emu/emu_audio_many.cpp - TEST INFRASTRUCTURE: gstamd_audio_converter_samples_many on the host the way the device
-// runs it - the same walk over the call's streams (aconv_many_run_length of audio_convert_plan.h), and for every batched run a loop over
-// the grid of each launch: blockIdx.y = stream, blockIdx.x up to the longest stream's blocks, 256 lanes, through the bodies the kernels
-// call (audio_convert_device.h aconv_pre_many_lane / _post_many_lane / _shape_many_lane) with the tables aconv_many_pre_entry /
-// _post_entry fill.  Mirrors gstamd_audio_converter_samples_many / aconv_run_many of audio_convert.hip.
+// tests/emu/emu_audio_many.cpp - TEST INFRASTRUCTURE: gstamd_audio_converter_samples_many on the host the way the
+// device runs it.  The call itself - the refusals, the walk with aconv_many_run_length, the stages of a batched run, the table entries, the
+// counters - is aconv_many_samples of audio_convert_plan.h, the function the library calls; this file is its host backend: for every
+// batched launch a loop over the grid through the body the kernel calls - k_aconv_pre_many / _pre_planes_many / _pre_mix_many /
+// k_aconv_wide_mix_many (two phases around its barrier, a host "LDS" of the kernel's size), k_aconv_post_many / _post_planes_many,
+// k_aconv_shape_many / _shape_planes_many (64 lanes, lane = stream).  Prefix "emu_aconv_many_".
 //
-// The converters are the emulator's existing handles: those of emu_aconv_planes_new (emu_audio_planes.cpp: every converter of at most 8
-// channels - interleaved, non-interleaved, passthrough, endian) and of emu_aconv_wide_new (emu_audio_wide.cpp), which the caller tells
-// apart in kind[].  A stream that is not batched goes through its own emulator's emu_aconv_*_samples.
+// The converters are the emulator's existing handles, told apart in kind[]: 0 of emu_aconv_planes_new (emu_audio_planes.cpp: every
+// converter of at most 8 channels), 1 of emu_aconv_wide_new (emu_audio_wide.cpp), 3 the latter with a resampler inside.  A stream that is
+// not batched goes through its own emulator's emu_aconv_*_samples.
+#include <algorithm>
 #include <cstring>
-#include <string>
+#include <deque>
 #include <vector>
 
 #include "../../gstreamer_amd/csrc/audio_convert_plan.h"
-#include "../../gstreamer_amd/csrc/audio_taps.h"
+#include "emu_audio_handles.h"
 
 using namespace gstamd;
 
@@ -20,157 +22,158 @@ extern "C" {
 void emu_audio_resample (void *h, const void *in, size_t in_frames, void *out, size_t out_frames);
 void emu_aconv_planes_samples (void *h, uint8_t *in, size_t in_frames, uint8_t *out, size_t out_frames);
 void emu_aconv_wide_samples (void *h, uint8_t *in, size_t in_frames, uint8_t *out, size_t out_frames);
-int emu_aconv_wide_is_passthrough (void *h);
 }
-
-// the handle of emu_aconv_planes_new: emu_audio_planes.cpp's definition, repeated token for token (one definition rule) - a change
-// there is a change here
-struct EmuAConvPlanes {
-  AConvPlan plan;
-  int in_layout = 0, out_layout = 0, flags = 0;
-  GstAmdAudioInfo in, out;
-  GstAmdAudioConverterConfig cfg;
-  bool resample = false, passthrough = false;
-  void *resampler = nullptr;
-  AConvDitherState dither = { 0xc2d6038fu, 0u, 0 };
-  AConvJump jump;
-  std::vector<int32_t> hist = std::vector<int32_t> (8 * GSTAMD_AUDIO_MAX_CHANNELS, 0);
-};
 
 namespace {
 
-enum { KIND_PLANES = 0, KIND_WIDE = 1, KIND_WIDE_RESAMPLER = 3 };
-
 thread_local int32_t many_debug[4] = { 0, 0, 0, 0 };
-const AConvPlan no_plan = {};                   // what a wide handle shows the decision: never looked at, `ordinary` is false
 
-// a stream as aconv_many_run_length sees it
-AConvManyItem item_of (void *h, int kind, bool has_input, size_t in_frames, size_t out_frames)
-{
-  if (kind & 1)
-    return { &no_plan, h, false, kind == KIND_WIDE_RESAMPLER, has_input, in_frames, out_frames };
-  const EmuAConvPlanes *c = (const EmuAConvPlanes *) h;
-  return { &c->plan, c, !c->in_layout && !c->out_layout && !c->passthrough, c->resampler != nullptr, has_input, in_frames, out_frames };
-}
+struct EmuManyBackend {
+  void *const *convs;
+  const int *kind;                              // NULL: all 0
+  std::deque<std::vector<uint8_t>> pool;        // the buffers of the run under way
 
-// aconv_run_many
-void many_run (int run, EmuAConvPlanes *const *cs, const uint8_t *const *in, const size_t *in_frames, uint8_t *const *out, const size_t *out_frames)
-{
-  const AConvPlan &p = cs[0]->plan;
-  const size_t mb = (size_t) amid_bytes (p.mid_in) * (size_t) p.out_ch;
-  const bool shape = aconv_plan_shapes (p), resample = cs[0]->resampler != nullptr;
-  std::vector<std::vector<uint8_t>> mid_a ((size_t) run), mid_b ((size_t) run);
-  std::vector<std::vector<int32_t>> q ((size_t) run);
-  for (int k = 0; k < run; k++) {
-    mid_a[(size_t) k].assign (in_frames[k] * mb, 0xcd);
-    mid_b[(size_t) k].assign ((out_frames[k] ? out_frames[k] : 1) * mb, 0xcd);
-    if (shape && out_frames[k])
-      q[(size_t) k].assign (out_frames[k] * (size_t) p.out_ch * 2, 0);
-  }
-  {                                             /* k_aconv_pre_many */
-    AConvManyPreTable t;
-    memset ((void *) &t, 0, sizeof (t));
-    size_t lanes = 0;
-    for (int k = 0; k < run; k++) {
-      const size_t l = aconv_many_pre_entry (p, in[k], in_frames[k], mid_a[(size_t) k].data (), &t.s[k]);
-      lanes = l > lanes ? l : lanes;
+  bool has_convs () const { return convs != nullptr; }
+
+  AConvManyConv conv (int i) const
+  {
+    void *h = convs[i];
+    if (!h)
+      return {};
+    if (kind && (kind[i] & 1)) {
+      EmuAConvWide *c = (EmuAConvWide *) h;
+      return { h, &c->plan.s, &c->plan, true, c->passthrough, c->in_layout, c->out_layout, c->resampler, &c->dither, &c->jump, c->hist.data (), &c->jump,
+        { c->plan.m.data (), c->plan.mi.data (), c->plan.use.data () } };
     }
-    const size_t grid = ((lanes + 255) / 256) * 256;
-#define PRE(K) for (int y = 0; y < run; y++) for (size_t x = 0; x < grid; x++) aconv_pre_many_lane<K> (p, t.s[y], x)
+    EmuAConvPlanes *c = (EmuAConvPlanes *) h;
+    return { h, &c->plan, nullptr, false, c->passthrough, c->in_layout, c->out_layout, c->resampler, &c->dither, &c->jump, c->hist.data (), &c->jump,
+      { nullptr, nullptr, nullptr } };
+  }
+
+  int fail (int code, const char *) { return code; }
+
+  int single (const AConvManyConv &c, const void *in, size_t in_frames, void *out, size_t out_frames)
+  {
+    (c.wide ? emu_aconv_wide_samples : emu_aconv_planes_samples) (c.h, (uint8_t *) in, in_frames, (uint8_t *) out, out_frames);
+    return GSTAMD_OK;
+  }
+
+  uint8_t *fresh (size_t bytes, uint8_t fill)
+  {
+    if (!bytes)
+      return nullptr;
+    pool.emplace_back (bytes, fill);
+    return pool.back ().data ();
+  }
+
+  int buffers (const AConvManyConv &, size_t mid_a_bytes, size_t mid_b_bytes, size_t q_bytes, AConvManyBuffers *b)
+  {
+    *b = { fresh (mid_a_bytes, 0xcd), fresh (mid_b_bytes, 0xcd), (int32_t *) fresh (q_bytes, 0) };
+    return GSTAMD_OK;
+  }
+
+  static size_t grid (size_t lanes) { return ((lanes + 255) / 256) * 256; }
+
+  void pre (const AConvPlan &p, const AConvManyPreTable &t, size_t lanes, int run)      /* blockIdx.y = stream */
+  {
+#define PRE(K) for (int y = 0; y < run; y++) for (size_t x = 0; x < grid (lanes); x++) aconv_pre_many_lane<K> (p, t.s[y], x)
     GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
 #undef PRE
-    many_debug[3]++;
   }
-  if (resample)                                 /* gstamd_audio_resampler_resample_many: independent streams, whatever the launch */
-    for (int k = 0; k < run; k++)
-      emu_audio_resample (cs[k]->resampler, mid_a[(size_t) k].data (), in_frames[k], mid_b[(size_t) k].data (), out_frames[k]);
-  AConvManyPostTable t;
-  AConvManyShapeTable sh;
-  memset ((void *) &t, 0, sizeof (t));
-  memset ((void *) &sh, 0, sizeof (sh));
-  size_t lanes = 0;
-  for (int k = 0; k < run; k++) {
-    int32_t *qk = shape && out_frames[k] ? q[(size_t) k].data () : nullptr;
-    const size_t l = aconv_many_post_entry (p, cs[k]->dither, resample ? mid_b[(size_t) k].data () : mid_a[(size_t) k].data (), out[k], out_frames[k], qk, &t.s[k]);
-    lanes = l > lanes ? l : lanes;
-    sh.s[k] = { qk, cs[k]->hist.data (), out[k], out_frames[k] };
+
+  void pre_planes (const AConvPlan &p, const AConvManyPrePlanesTable &t, size_t lanes, int run)        /* blockIdx.y = output channel, blockIdx.z = stream */
+  {
+#define PRE(K) for (int z = 0; z < run; z++) for (int y = 0; y < p.out_ch; y++) for (size_t x = 0; x < grid (lanes); x++) aconv_pre_planes_many_lane<K> (p, t.s[z], y, x)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
   }
-  if (lanes) {
-    const size_t grid = ((lanes + 255) / 256) * 256;
-#define POST(K) for (int y = 0; y < run; y++) for (size_t x = 0; x < grid; x++) aconv_post_many_lane<K> (p, cs[0]->jump, t.s[y], x)
-    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);   /* k_aconv_post_many */
+
+  void pre_mix (const AConvPlan &p, const AConvManyPreTable &t, size_t lanes, int run)
+  {
+#define PRE(K) for (int z = 0; z < run; z++) for (int y = 0; y < p.out_ch; y++) for (size_t x = 0; x < grid (lanes); x++) aconv_pre_mix_many_lane<K> (p, t.s[z], y, x)
+    GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+  }
+
+  /* blockIdx.x = tile, blockIdx.y = stream, 256 lanes, a barrier between the phases */
+  void wide_mix (const AConvPlan &p, const AConvWideMatrix &w, const AConvManyPrePlanesTable &t, int in_layout, int tile, size_t tiles, int run)
+  {
+    std::vector<uint8_t> lds (aconv_wide_lds_bytes (p, tile));
+    for (int y = 0; y < run; y++)
+      for (size_t bx = 0; bx < tiles; bx++) {
+        const AConvManyPrePlanes &m = t.s[y];
+        size_t n0;
+        int nf;
+        if (!aconv_wide_many_tile (m, bx, tile, &n0, &nf))
+          continue;
+        std::fill (lds.begin (), lds.end (), (uint8_t) 0xcd);                   /* a workgroup finds LDS as whoever ran before left it */
+        uint8_t *x = lds.data (), *mat = lds.data () + aconv_wide_x_bytes (p, tile);
+        for (int tid = 0; tid < 256; tid++) {
+          if (p.mix)
+            aconv_wide_stage_matrix (p, w, mat, tid, 256);
+#define PRE(K) aconv_wide_stage_lane<K> (p, aconv_many_side (m.in, akind_bytes (K)), in_layout, n0, nf, x, tid, 256)
+          GSTAMD_ACONV_FOR_KIND (p.in_kind, PRE);
+#undef PRE
+        }
+        for (int tid = 0; tid < 256; tid++)
+          aconv_wide_mix_lane (p, x, mat, w.use, m.mid, n0, nf, tid, 256);
+      }
+  }
+
+  void post (const AConvPlan &p, const AConvJump *jump, const AConvManyPostTable &t, size_t lanes, int run)
+  {
+#define POST(K) for (int y = 0; y < run; y++) for (size_t x = 0; x < grid (lanes); x++) aconv_post_many_lane<K> (p, *jump, t.s[y], x)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
 #undef POST
-    many_debug[3]++;
-    if (shape) {                                /* k_aconv_shape_many: blockIdx.x = stream, 64 lanes */
-#define SHAPE(K) for (int y = 0; y < run; y++) for (int c = 0; c < 64; c++) aconv_shape_many_lane<K> (p, sh.s[y], c)
-      GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
-#undef SHAPE
-      many_debug[3]++;
-    }
   }
-  for (int k = 0; k < run; k++)
-    aconv_dither_advance (p, cs[k]->jump, &cs[k]->dither, out_frames[k] * (size_t) p.out_ch);
-}
+
+  void post_planes (const AConvPlan &p, const AConvJump *jump, const AConvManyPostPlanesTable &t, size_t lanes, int run)
+  {
+#define POST(K) for (int z = 0; z < run; z++) for (int y = 0; y < p.out_ch; y++) for (size_t x = 0; x < grid (lanes); x++) \
+    aconv_post_planes_many_lane<K> (p, *jump, t.s[z], y, x)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, POST);
+#undef POST
+  }
+
+  void shape (const AConvPlan &p, const AConvManyShapeTable &sh, int run)       /* blockIdx.x = stream, 64 lanes */
+  {
+#define SHAPE(K) for (int y = 0; y < run; y++) for (int c = 0; c < 64; c++) aconv_shape_many_lane<K> (p, sh.s[y], c)
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+  }
+
+  void shape_planes (const AConvPlan &p, const AConvManyShapeTable &sh)         /* one workgroup, lane = stream */
+  {
+#define SHAPE(K) for (int lane = 0; lane < 64; lane++) aconv_shape_planes_many_lane<K> (p, sh.s[lane])
+    GSTAMD_ACONV_FOR_KIND (p.out_kind, SHAPE);
+#undef SHAPE
+  }
+
+  /* gstamd_audio_resampler_resample_many: independent streams, whatever the launch */
+  int resample_many (int run, const AConvManyConv *cs, const AConvManyBuffers *b, const size_t *in_frames, const size_t *out_frames)
+  {
+    for (int k = 0; k < run; k++)
+      emu_audio_resample (cs[k].resampler, b[k].mid_a, in_frames[k], b[k].mid_b, out_frames[k]);
+    return GSTAMD_OK;
+  }
+
+  /* the run's last launch is over: its buffers go, as device scratch would be free for the next run */
+  int launched ()
+  {
+    pool.clear ();
+    return GSTAMD_OK;
+  }
+};
 
 }  // namespace
 
 extern "C" {
 
-// gstamd_audio_converter_samples_many over emulator handles; kind[i]: 0 a handle of emu_aconv_planes_new, 1 of emu_aconv_wide_new, 3 the
-// latter with a resampler inside (NULL: all 0).  Returns GSTAMD_OK or GSTAMD_ERR_INVALID, as the C ABI does.
-int emu_aconv_many_samples (int n, void *const *handles, const int *kind, uint8_t *const *in, const size_t *in_frames, uint8_t *const *out, const size_t *out_frames)
+// gstamd_audio_converter_samples_many over emulator handles.  Returns GSTAMD_OK or GSTAMD_ERR_INVALID, as the C ABI does.
+int emu_aconv_many_samples (int n, void *const *handles, const int *kind, const void *const *in, const size_t *in_frames, void *const *out, const size_t *out_frames)
 {
-  memset (many_debug, 0, sizeof (many_debug));
-  if (n < 0 || (n > 0 && (!handles || !in_frames || !out_frames)))
-    return GSTAMD_ERR_INVALID;
-  auto wide = [&](int i) { return kind && (kind[i] & 1); };
-  for (int i = 0; i < n; i++) {
-    if (!handles[i] || (out_frames[i] && (!out || !out[i])))
-      return GSTAMD_ERR_INVALID;
-    if (in_frames[i] == 0)
-      continue;
-    const bool resampler = wide (i) ? kind[i] == KIND_WIDE_RESAMPLER : ((EmuAConvPlanes *) handles[i])->resampler != nullptr;
-    const bool passthrough = wide (i) ? emu_aconv_wide_is_passthrough (handles[i]) != 0 : ((EmuAConvPlanes *) handles[i])->passthrough;
-    if (!resampler && !(in && in[i]))
-      return GSTAMD_ERR_INVALID;
-    if (!resampler && !passthrough && in_frames[i] != out_frames[i])
-      return GSTAMD_ERR_INVALID;
-  }
-  std::vector<AConvManyItem> items;
-  std::vector<int> at;
-  for (int i = 0; i < n; i++) {
-    if (in_frames[i] == 0)
-      continue;
-    items.push_back (item_of (handles[i], kind ? kind[i] : 0, in && in[i] != nullptr, in_frames[i], out_frames[i]));
-    at.push_back (i);
-  }
-  const int live = (int) items.size ();
-  for (int done = 0; done < live;) {
-    const int run = aconv_many_run_length (&items[(size_t) done], live - done);
-    if (run < 2) {
-      const int i = at[(size_t) done];
-      (wide (i) ? emu_aconv_wide_samples : emu_aconv_planes_samples) (handles[i], in ? in[i] : nullptr, in_frames[i], out ? out[i] : nullptr, out_frames[i]);
-      many_debug[2]++;
-    } else {
-      EmuAConvPlanes *cs[GSTAMD_ACONV_MANY_MAX];
-      const uint8_t *ip[GSTAMD_ACONV_MANY_MAX];
-      uint8_t *op[GSTAMD_ACONV_MANY_MAX];
-      size_t inf[GSTAMD_ACONV_MANY_MAX], outf[GSTAMD_ACONV_MANY_MAX];
-      for (int k = 0; k < run; k++) {
-        const int i = at[(size_t) (done + k)];
-        cs[k] = (EmuAConvPlanes *) handles[i];
-        ip[k] = in[i];
-        op[k] = out ? out[i] : nullptr;
-        inf[k] = in_frames[i];
-        outf[k] = out_frames[i];
-      }
-      many_run (run, cs, ip, inf, op, outf);
-      many_debug[0]++;
-      many_debug[1] += run;
-    }
-    done += run;
-  }
-  return GSTAMD_OK;
+  EmuManyBackend be = { handles, kind, {} };
+  return aconv_many_samples (be, n, in, in_frames, out, out_frames, many_debug);
 }
 
 int emu_aconv_many_debug (int32_t *out, int max_out)
@@ -181,12 +184,12 @@ int emu_aconv_many_debug (int32_t *out, int max_out)
 }
 
 // aconv_many_run_length over the same handles, for a test that states the runs: the length of the run that starts at stream 0
-int emu_aconv_many_run_length (int n, void *const *handles, const int *kind, uint8_t *const *in, const size_t *in_frames, const size_t *out_frames)
+int emu_aconv_many_run_length (int n, void *const *handles, const int *kind, const void *const *in, const size_t *in_frames, const size_t *out_frames)
 {
+  const EmuManyBackend be = { handles, kind, {} };
   std::vector<AConvManyItem> items;
-  for (int i = 0; i < n; i++) {
-    items.push_back (item_of (handles[i], kind ? kind[i] : 0, in && in[i] != nullptr, in_frames[i], out_frames[i]));
-  }
+  for (int i = 0; i < n; i++)
+    items.push_back (aconv_many_item (be.conv (i), in && in[i] != nullptr, in_frames[i], out_frames[i]));
   return aconv_many_run_length (items.data (), n);
 }
 

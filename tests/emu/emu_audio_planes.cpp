@@ -10,6 +10,7 @@
 
 #include "../../gstreamer_amd/csrc/audio_convert_plan.h"
 #include "../../gstreamer_amd/csrc/audio_taps.h"
+#include "emu_audio_handles.h"
 
 using namespace gstamd;
 
@@ -20,18 +21,6 @@ void emu_audio_free (void *h);
 size_t emu_audio_get_out_frames (void *h, size_t in_frames);
 void emu_audio_resample (void *h, const void *in, size_t in_frames, void *out, size_t out_frames);
 }
-
-struct EmuAConvPlanes {
-  AConvPlan plan;
-  int in_layout = 0, out_layout = 0, flags = 0;
-  GstAmdAudioInfo in, out;
-  GstAmdAudioConverterConfig cfg;
-  bool resample = false, passthrough = false;
-  void *resampler = nullptr;
-  AConvDitherState dither = { 0xc2d6038fu, 0u, 0 };
-  AConvJump jump;
-  std::vector<int32_t> hist = std::vector<int32_t> (8 * GSTAMD_AUDIO_MAX_CHANNELS, 0);
-};
 
 static void *planes_new_resampler (EmuAConvPlanes *c, char *err, int err_len)
 {

@@ -10,6 +10,7 @@
 
 #include "../../gstreamer_amd/csrc/audio_convert_plan.h"
 #include "../../gstreamer_amd/csrc/audio_taps.h"
+#include "emu_audio_handles.h"
 
 using namespace gstamd;
 
@@ -22,17 +23,6 @@ void emu_audio_resample (void *h, const void *in, size_t in_frames, void *out, s
 }
 
 namespace {
-
-struct EmuAConvWide {
-  AConvWidePlan plan;
-  int in_layout = 0, out_layout = 0, flags = 0, in_rate = 0, out_rate = 0;
-  GstAmdAudioConverterConfig cfg;
-  bool resample = false, passthrough = false;
-  void *resampler = nullptr;
-  AConvDitherState dither = { 0xc2d6038fu, 0u, 0 };
-  AConvJump jump;
-  std::vector<int32_t> hist = std::vector<int32_t> (8 * GSTAMD_AUDIO_MAX_CHANNELS_WIDE, 0);
-};
 
 void *wide_new_resampler (EmuAConvWide *c, char *err, int err_len)
 {

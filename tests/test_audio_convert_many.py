@@ -10,8 +10,10 @@ A. equal plans, streams of unequal length whose buffers start 0 .. 3 samples int
 C. a mixed array: two plans alternating, a wide converter, a non-interleaved output, a passthrough, an endian plan;  D. the same converter twice;
 E. more than 64 streams;  F. n = 0, an empty stream inside a run, the refusals;  G. emulator and device agree byte for byte (GPU only).
 
-Every check runs twice: -m "not gpu" through the kernel bodies on the host emulator (tests/emu/emu_audio_many.cpp walks the grid of each batched
-launch), -m gpu through the C ABI on the device.  Output blocks sit between guard bytes that must survive."""
+Every check runs twice: -m "not gpu" through the kernel bodies on the host emulator (tests/emu/emu_audio_many.cpp: the library's own walk of the
+call, aconv_many_samples of audio_convert_plan.h, over a backend that loops over the grid of each batched launch), -m gpu through the C ABI on the
+device.  There is one run rule (aconv_many_run_length) and one emulator of it; tests/test_audio_convert_many_layouts.py uses the same one.  Output
+blocks sit between guard bytes that must survive."""
 import ctypes as C
 
 import numpy as np

@@ -12,9 +12,8 @@ H. emulator and device agree byte for byte (GPU only).
 
 A non-interleaved side is one block, plane after plane (what gstamd_audio_converter_samples takes); blocks start 0 .. 3 samples into their
 allocations and sit between guard bytes that must survive.  Every check runs twice: -m "not gpu" through the kernel bodies on the host emulator
-(tests/emu/emu_audio_many_layouts.cpp walks the grid of each batched launch), -m gpu through the C ABI on the device."""
-import ctypes as C
-
+(tests/emu/emu_audio_many.cpp, the one emulator of the call: the library's own walk, aconv_many_samples of audio_convert_plan.h, over a backend
+that loops over the grid of each batched launch), -m gpu through the C ABI on the device."""
 import numpy as np
 import pytest
 
@@ -37,32 +36,13 @@ class Plan(M.Plan):
 
 
 class EmuMany(M.EmuMany):
-    """tests/emu/emu_audio_many_layouts.cpp over the handles of emu_audio_planes.cpp / emu_audio_wide.cpp"""
-
-    def __init__(self, emu):
-        M.EmuMany.__init__(self, emu)
-        pp, ps = C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)
-        emu.emu_aconv_many_layouts_samples.argtypes = [C.c_int, pp, C.POINTER(C.c_int), pp, ps, pp, ps]
-        emu.emu_aconv_many_layouts_debug.argtypes = [C.POINTER(C.c_int32), C.c_int]
-        emu.emu_aconv_many_layouts_run_length.argtypes = [C.c_int, pp, C.POINTER(C.c_int), pp, ps, ps]
+    """M.EmuMany (tests/emu/emu_audio_many.cpp) with the mix matrix of a wide converter"""
 
     def new(self, plan):
         if not plan.wide:
             return M.EmuMany.new(self, plan)
         ii, oi = plan.infos()
         return self.wide.new(ii, plan.il, oi, plan.ol, A.audio_converter_config(**plan.cfg), plan.matrix), plan.kind
-
-    def many(self, convs, srcs, in_frames, dsts, out_frames):
-        return self.emu.emu_aconv_many_layouts_samples(*self._arrays(convs, srcs, in_frames, dsts, out_frames))
-
-    def run_length(self, convs, srcs, in_frames, out_frames):
-        n, hs, kinds, ip, inf, _, outf = self._arrays(convs, srcs, in_frames, [None] * len(convs), out_frames)
-        return self.emu.emu_aconv_many_layouts_run_length(n, hs, kinds, ip, inf, outf)
-
-    def debug(self):
-        buf = (C.c_int32 * 4)()
-        assert self.emu.emu_aconv_many_layouts_debug(buf, 4) == 4
-        return list(buf)
 
 
 class GpuMany(M.GpuMany):
