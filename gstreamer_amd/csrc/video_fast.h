@@ -367,10 +367,9 @@ GSTAMD_HD void layout_init (uint32_t (&q)[4][2])
 // four pixels of one line.  yw: luma bytes y0..y3; xh[j]: blended chroma of pixel j in the high bytes of the u16 lanes
 // (already XOR 0x80).  Step-major order keeps dependent SDWA instructions apart (gfx950 needs a wait state between them).
 template <int L, int ABL>
-GSTAMD_HD void fast_emit4_l (const FastParams &fp, uint8_t *__restrict__ d, bool store, uint32_t yw, const uint32_t *xh, uint32_t (&q)[4][2])
+GSTAMD_HD void fast_px4_l (const FastParams &fp, uint32_t yw, const uint32_t *xh, uint32_t (&q)[4][2], uint32_t (&o)[4])
 {
   constexpr int PR = L & 3, PG = (L >> 2) & 3, PB = (L >> 4) & 3;
-  uint32_t o[4];
   if (ABL == 1) {
 #pragma unroll
     for (int j = 0; j < 4; j++)
@@ -424,6 +423,14 @@ GSTAMD_HD void fast_emit4_l (const FastParams &fp, uint8_t *__restrict__ d, bool
     for (int j = 0; j < 4; j++)
       o[j] = fast_lut3_px (o[j], fp.lut_keep);
   }
+}
+
+// ... and their store, with the store policy of the launch
+template <int L, int ABL>
+GSTAMD_HD void fast_emit4_l (const FastParams &fp, uint8_t *__restrict__ d, bool store, uint32_t yw, const uint32_t *xh, uint32_t (&q)[4][2])
+{
+  uint32_t o[4];
+  fast_px4_l<L, ABL> (fp, yw, xh, q, o);
   if (store) {
     if (fp.px_bytes == 3)                   // wave-uniform
       store12_stream (d, o[0], o[1], o[2], o[3]);
@@ -552,6 +559,130 @@ GSTAMD_HD void fast_strip (const FastParams &fp, const Planes &pl, uint8_t *__re
       cprev[i] = ccur[i];
   }
 }
+
+// ---- interior strips: the same pairs as straight-line code --------------------------------------------------------
+// A wave whose pairs all have both lines, whose chroma rows all exist without a clamp and whose lanes all load the sample
+// right of their span with it (not the row's last 256-pixel column) needs none of fast_strip's case distinctions.  Its
+// steady loop is: loads of pair p + 1, math of pair p, two unconditional stores; the last pair (no prefetch) is peeled.
+// The stores are buffer stores on a resource made from the frame's wave-uniform destination pointer, emitted through
+// the builtin so that the compiler counts them: loads and stores share vmcnt on gfx950, and with the inline-asm stores
+// of store16_policy the counted wait for the next pair's luma also waits for the two write-through stores of the pair
+// just finished - every wave drained to memory once per pair.  Here the waits leave both stores in flight under the
+// next pair's math.  POLICY (store16_policy's numbering) is a template argument: 1 (sc0 sc1) and 3 (sc0 sc1 nt), the
+// two the launcher chooses by itself; pinned policies 0 / 2 / 4 keep fast_strip.  Integers and bytes are fast_strip's.
+GSTAMD_HD bool fast_strip_is_interior (const FastParams &fp, int dstride, int col, int p_begin, int p_end)
+{
+  const int cw = (fp.width + 1) >> 1;
+  return fp.px_bytes == 4 && p_begin >= 1 && p_end > p_begin && 2 * (p_end - 1) < fp.height    /* both lines of every pair */
+      && p_begin - 1 >= fp.crow_lo && p_end - 1 <= fp.crow_hi                                   /* no clamped chroma row */
+      && col * 128 + 128 < cw                                                                   /* k0 + 2 < cw on lane 63 */
+      && dstride > 0 && (long long) fp.height * dstride < 0x7fffffffLL;                         /* 32-bit buffer offsets */
+}
+
+#ifdef __HIPCC__
+template <int POLICY>
+__device__ __forceinline__ void store16_buffer (__amdgpu_buffer_rsrc_t rsrc, uint32_t lane_off, uint32_t line_off, const uint32_t (&o)[4])
+{
+  typedef unsigned int u32x4 __attribute__ ((ext_vector_type (4)));
+  static_assert (POLICY == 1 || POLICY == 3, "the write-through policies only");
+  const u32x4 v = {o[0], o[1], o[2], o[3]};
+  /* aux: 1 = sc0, 2 = nt, 16 = sc1.  The wave-uniform line offset is added into the vector offset on purpose: with an SGPR in the scalar-offset
+     field hipcc (ROCm 7) takes a 16-byte buffer store to be free of the "VALU overwrites the store's data registers" hazard and puts no wait state
+     behind it, and on gfx950 the next instruction's write to the first data register then reached lanes 12-15 of every 16 before the store had
+     read them (measured: one wrong pixel per such lane, the peeled pair's first line).  With the field at zero it inserts the s_nop itself. */
+  __builtin_amdgcn_raw_buffer_store_b128 (v, rsrc, lane_off + line_off, 0, POLICY == 1 ? (1 | 16) : (1 | 2 | 16));
+}
+
+// chroma_load4 where the sample right of the span always rides in the load (k0 + 2 < cw)
+template <int CH>
+__device__ __forceinline__ void chroma_load4_inner (const uint8_t *__restrict__ row, int x0, ChromaRaw4 &r)
+{
+  const int k0 = x0 >> 1;
+  const uint8_t *p = row + 2 * (size_t) k0;
+  r.nxt = r.prv_hi = 0;
+  if (CH != CHROMA_H_NONE) {
+    const u32x2u m = *(const u32x2u *) p;
+    r.raw = m.a;
+    r.nxt = m.b;
+  } else
+    r.raw = *(const uint32_t *) p;
+  if (CH == CHROMA_H_H2)
+    r.prv_hi = (uint32_t) * (const uint16_t *) (row + 2 * (size_t) (k0 > 0 ? k0 - 1 : 0)) << 16;
+}
+
+template <int CH, int L, int ABL, int POLICY>
+__device__ __forceinline__ void fast_strip_interior (const FastParams &fp, const Planes &pl, uint8_t *__restrict__ dst, int dstride, int x0, int p_begin,
+    int p_end)
+{
+  const uint8_t *yb = pl.p[0] + x0, *cbase = pl.p[1];
+  const int ys = pl.stride[0], cs = pl.stride[1];
+  /* the frame's real extent: a store past it would be dropped, none is */
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc (dst, 0, (fp.height - 1) * dstride + 4 * fp.width, 0x00020000);
+  const uint32_t lane_off = 4u * (uint32_t) x0;
+  uint32_t q[4][2];
+  layout_init<L> (q);
+
+  uint32_t cprev[4], ccur[4], c0[4], c1[4], o0[4], o1[4];
+  ChromaRaw4 craw, r0;
+  uint32_t y0, y1;
+  chroma_load4_inner<CH> (cbase + (ptrdiff_t) (p_begin - 1) * cs, x0, r0);
+  chroma_load4_inner<CH> (cbase + (ptrdiff_t) p_begin * cs, x0, craw);
+  y0 = load_stream32 (yb + (size_t) (2 * p_begin - 1) * ys);
+  y1 = load_stream32 (yb + (size_t) (2 * p_begin) * ys);
+  chroma_filter4<CH> (r0.raw, r0.nxt, r0.prv_hi, cprev);
+  /* the first pair's loads are waited for here: the loop is entered with nothing outstanding on either edge, and the waits inside it count
+     from its own loads and stores alone (an entry state with loads pending would turn them into waits for the stores) */
+  asm volatile ("" : "+v" (y0), "+v" (y1), "+v" (craw.raw), "+v" (craw.nxt), "+v" (craw.prv_hi));
+  uint32_t line_off = (uint32_t) (2 * p_begin - 1) * (uint32_t) dstride;
+  for (int p = p_begin; p + 1 < p_end; p++) {
+    const uint32_t cy0 = y0, cy1 = y1;
+    const ChromaRaw4 cr_now = craw;
+    chroma_load4_inner<CH> (cbase + (ptrdiff_t) (p + 1) * cs, x0, craw);
+    y0 = load_stream32 (yb + (size_t) (2 * p + 1) * ys);
+    y1 = load_stream32 (yb + (size_t) (2 * p + 2) * ys);
+    chroma_filter4<CH> (cr_now.raw, cr_now.nxt, cr_now.prv_hi, ccur);
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+      blend_rows_hi (cprev[j], ccur[j], c0[j], c1[j]);
+    fast_px4_l<L, ABL> (fp, cy0, c0, q, o0);
+    store16_buffer<POLICY> (rsrc, lane_off, line_off, o0);
+    __builtin_amdgcn_sched_barrier (0);         /* the first line leaves before the second is made: its four registers are free for it */
+    fast_px4_l<L, ABL> (fp, cy1, c1, q, o1);
+    store16_buffer<POLICY> (rsrc, lane_off, line_off + (uint32_t) dstride, o1);
+    line_off += 2u * (uint32_t) dstride;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+      cprev[i] = ccur[i];
+    /* the one wait of the loop: the next pair's loads, issued a whole pair's math ago; the two stores stay in flight (vmcnt (2)).  The
+       scheduling barrier keeps the compiler's copies of the loaded registers, and with them their wait, from moving up between the stores */
+    __builtin_amdgcn_sched_barrier (0);
+    asm volatile ("" : "+v" (y0), "+v" (y1), "+v" (craw.raw), "+v" (craw.nxt), "+v" (craw.prv_hi));
+  }
+  chroma_filter4<CH> (craw.raw, craw.nxt, craw.prv_hi, ccur);
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+    blend_rows_hi (cprev[j], ccur[j], c0[j], c1[j]);
+  fast_px4_l<L, ABL> (fp, y0, c0, q, o0);
+  store16_buffer<POLICY> (rsrc, lane_off, line_off, o0);
+  fast_px4_l<L, ABL> (fp, y1, c1, q, o1);
+  store16_buffer<POLICY> (rsrc, lane_off, line_off + (uint32_t) dstride, o1);
+}
+
+// fast_strip, or its straight-line form where the wave qualifies (wave-uniform, decided once per wave)
+template <int CH, int L, int ABL>
+__device__ __forceinline__ void fast_strip_wave (const FastParams &fp, const Planes &pl, uint8_t *__restrict__ dst, int dstride, int col, int x0, int p_begin,
+    int p_end)
+{
+  if (ABL == 0 && fast_strip_is_interior (fp, dstride, col, p_begin, p_end)) {
+    if (fp.store_policy == 1)
+      return fast_strip_interior<CH, L, ABL, 1> (fp, pl, dst, dstride, x0, p_begin, p_end);
+    if (fp.store_policy == 3)
+      return fast_strip_interior<CH, L, ABL, 3> (fp, pl, dst, dstride, x0, p_begin, p_end);
+  }
+  if (x0 + 4 <= fp.width)
+    fast_strip<CH, L, ABL> (fp, pl, dst, dstride, x0, p_begin, p_end);
+}
+#endif
 
 // ---- wide variant: one wave = a 1024-pixel run of ONE line pair, staged through LDS ---------------------
 // Every source row segment is fetched with ONE 16-byte load per lane (1 KB contiguous per wave instruction), parked in

@@ -1491,8 +1491,7 @@ __global__ __launch_bounds__ (64) void k_convert_strip (FastParams fp, FrameBatc
   const Planes pl = batch_planes (batch, blockIdx.z);
   const int x0 = (blockIdx.x * 64 + threadIdx.x) * 4;
   const int p0 = blockIdx.y * K;
-  if (x0 + 4 <= fp.width)
-    fast_strip<CH, L, ABL> (fp, pl, batch.dst[blockIdx.z], batch.dstride, x0, p0, p0 + K < pairs ? p0 + K : pairs);
+  fast_strip_wave<CH, L, ABL> (fp, pl, batch.dst[blockIdx.z], batch.dstride, blockIdx.x, x0, p0, p0 + K < pairs ? p0 + K : pairs);
 }
 
 // the same under the XCD-aware block order of the wide kernel (wide_block_map): 1-D grid
@@ -1509,8 +1508,7 @@ __global__ __launch_bounds__ (64) void k_convert_strip_xcd (FastParams fp, Frame
   const int z = S / strips, p0 = (S - z * strips) * K;
   const Planes pl = batch_planes (batch, z);
   const int x0 = (col * 64 + threadIdx.x) * 4;
-  if (x0 + 4 <= fp.width)
-    fast_strip<CH, L, ABL> (fp, pl, batch.dst[z], batch.dstride, x0, p0, p0 + K < pairs ? p0 + K : pairs);
+  fast_strip_wave<CH, L, ABL> (fp, pl, batch.dst[z], batch.dstride, col, x0, p0, p0 + K < pairs ? p0 + K : pairs);
 }
 
 // destination byte order -> layout template argument (the four orders of the eight 4-byte RGB formats)
@@ -1613,12 +1611,16 @@ static const FastVariant &fast_variant ()
 template <int CH>
 static bool launch_fast (const FastParams &fp, const FrameBatch &batch, int n, hipStream_t stream)
 {
-  /* shipped configuration (MI355X sweeps, profiles/r01_c2_variants.txt): strip kernel, 4-pixel columns, 3 line pairs per
-   * lane with the next pair's loads in flight during the current pair's math, one wave per workgroup */
+  /* shipped configuration (MI355X sweeps, profiles/r01_c2_variants.txt): strip kernel, 4-pixel columns, 2 or 3 line pairs per
+   * lane (below) with the next pair's loads in flight during the current pair's math, one wave per workgroup */
   const FastVariant &v = fast_variant ();
   /* (one frame of less than 6 M pixels per launch: two pairs per lane - half again as many waves to fill the chip with; 2560 x 1440: 8.1 -> 6.7 us,
-     scripts/strip_k_probe.py, round 6; at 4K and in lists three pairs stay) */
-  const int k_default = n == 1 && (long) fp.width * fp.height < 6000000L ? 2 : 3;
+     scripts/strip_k_probe.py, round 6; at 4K and in lists three pairs stayed for the forms that run fast_strip alone) */
+  /* (with the interior strips on the straight-line path - 4-byte pixels, no table - two pairs win at every launch size: 4K, K = 3 -> 2 on one box,
+     one frame per launch 12.21 -> 11.87 us, lists of 4 9.08 -> 8.69, of 8 8.48 -> 8.14, of 32 7.13 -> 7.05; K = 3 had been chosen under the per-pair
+     store drain; profiles/r07/strip_waits.md) */
+  const bool straight = fp.px_bytes == 4 && !fp.lut;
+  const int k_default = straight || (n == 1 && (long) fp.width * fp.height < 6000000L) ? 2 : 3;
   const int shape = v.set ? v.shape : 0, K = v.set && v.K > 0 ? v.K : k_default;
 #ifdef GSTAMD_TUNING       /* memory-only ablation (wrong pixels on purpose): profiling builds only, never in the product library */
   if (v.set && v.abl && CH == CHROMA_H_H2_CS)
