@@ -622,6 +622,9 @@ int gstamd_compositor_blend (int format, int overlay, const void *src, int sw, i
 
 int gstamd_compositor_fill_checker (int format, void *dest, int dw, int dh, int dstride, int y_start, int y_end, void *stream)
 {
+  /* the rows of the canvas only: the reference's fill loops trust their caller, an entry that is told the height does not write past it */
+  y_start = y_start < 0 ? 0 : y_start;
+  y_end = y_end > dh ? dh : y_end;
   if (is_wide64 (format) && dest) {
     Wide64Params w;
     memset (&w, 0, sizeof (w));
@@ -643,6 +646,8 @@ int gstamd_compositor_fill_checker (int format, void *dest, int dw, int dh, int 
 int gstamd_compositor_fill_color (int format, void *dest, int dw, int dh, int dstride, int y_start, int y_end, int c1,
     int c2, int c3, void *stream)
 {
+  y_start = y_start < 0 ? 0 : y_start;
+  y_end = y_end > dh ? dh : y_end;
   if (is_wide64 (format) && dest) {
     /* fill_color_argb64 (blend.c:1354-1384): the picture's pixels, 16-bit components */
     Wide64Params w;

@@ -368,7 +368,8 @@ int gstamd_compositor_blend (int format, int overlay, const void *src, int sw, i
     int xpos, int ypos, double src_alpha, void *dest, int dw, int dh, int dstride,
     int dst_y_start, int dst_y_end, int mode, void *stream);
 
-/* FillCheckerFunction / FillColorFunction (blend.h:51-52) on rows [y_start, y_end). */
+/* FillCheckerFunction / FillColorFunction (blend.h:51-52) on rows [y_start, y_end) of the canvas (a window that reaches past `dh` ends at the
+ * last row). */
 int gstamd_compositor_fill_checker (int format, void *dest, int dw, int dh, int dstride,
     int y_start, int y_end, void *stream);
 int gstamd_compositor_fill_color (int format, void *dest, int dw, int dh, int dstride,

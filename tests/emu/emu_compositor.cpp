@@ -181,6 +181,10 @@ static void run_impl (const AggregateParams *p, const OpacityMaps *om, uint8_t *
       }
     return;
   }
+  /* as launch (): a continuation chunk that cannot take the direct form takes k_aggregate's per-pixel form - the packed span would force the alpha byte
+   * of pixels no pad of this chunk touches */
+  if (q.bg_kind == 2)
+    q.fast = 0;
   for (int y = ry0; y < ry0 + rh; y++)
     for (int gx = 0; gx < rw; gx += 4) {
       const int bx0 = rx0 + (gx / 256) * 256, bx1 = bx0 + 256 < rx0 + rw ? bx0 + 256 : rx0 + rw;    /* the wave's strip */
