@@ -438,3 +438,57 @@ def mixer_debug():
     buf = (C.c_int32 * 4)()
     _mix_lib().gstamd_audio_mixer_debug_launches(buf, 4)
     return dict(zip(("launches", "mixed", "skipped"), list(buf)[:3]))
+
+
+# ---- volume (include/gstamd_audio.h) -------------------------------------------------------------------------------------------
+class VolumeBuffer(C.Structure):
+    """GstAmdAudioVolumeBuffer: out == in works in place; gains NULL: the fixed volume, else one double per frame"""
+    _fields_ = [("in_", C.c_void_p), ("out", C.c_void_p), ("frames", C.c_uint64), ("volume", C.c_double), ("gains", C.c_void_p),
+                ("mute", C.c_int32), ("reserved", C.c_int32)]
+
+
+_vol_ready = False
+
+
+def _vol_lib():
+    global _vol_ready
+    L = lib()
+    if not _vol_ready:
+        L.gstamd_audio_volume_process.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_double, C.c_int, C.c_void_p,
+                                                  C.c_void_p]
+        L.gstamd_audio_volume_process_many.argtypes = [C.c_int, C.c_int, C.POINTER(VolumeBuffer), C.c_int, C.c_void_p]
+        L.gstamd_audio_volume_debug_launches.argtypes = [C.POINTER(C.c_int32), C.c_int]
+        _vol_ready = True
+    return L
+
+
+def volume_buffer(src, dst, frames, volume=1.0, mute=False, gains=None):
+    """src, dst, gains: device pointers or buffers (torch CUDA tensors); dst None: in place"""
+    s = None if src is None else _ptr(src)
+    return VolumeBuffer(s, s if dst is None else _ptr(dst), frames, volume, None if gains is None else _ptr(gains), int(mute), 0)
+
+
+def volume_buffers(buffers):
+    """the array gstamd_audio_volume_process_many takes, from VolumeBuffer objects"""
+    return (VolumeBuffer * len(buffers))(*buffers)
+
+
+def volume_process(fmt, channels, src, dst, frames, volume=1.0, mute=False, gains=None, stream=None):
+    """gstamd_audio_volume_process: one buffer; dst None: in place.  Asynchronous on `stream`."""
+    s = None if src is None else _ptr(src)
+    _v._check(_vol_lib().gstamd_audio_volume_process(AFMT[fmt] if isinstance(fmt, str) else fmt, channels, s, s if dst is None else _ptr(dst),
+                                                     frames, volume, int(mute), None if gains is None else _ptr(gains), stream))
+
+
+def volume_process_many(fmt, channels, buffers, stream=None):
+    """gstamd_audio_volume_process_many: buffers (a list of VolumeBuffer, or a volume_buffers array), one launch per 64 buffers that need
+    the kernel; fmt: a name of AFMT or a GSTAMD_AFMT_* value.  Asynchronous on `stream`."""
+    arr = buffers if isinstance(buffers, C.Array) else volume_buffers(buffers)
+    _v._check(_vol_lib().gstamd_audio_volume_process_many(AFMT[fmt] if isinstance(fmt, str) else fmt, channels, arr, len(arr), stream))
+
+
+def volume_debug():
+    """what this thread's last volume_process / volume_process_many did (gstamd_audio_volume_debug_launches)"""
+    buf = (C.c_int32 * 4)()
+    _vol_lib().gstamd_audio_volume_debug_launches(buf, 4)
+    return dict(zip(("launches", "scaled", "passed", "silenced"), list(buf)))

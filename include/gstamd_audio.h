@@ -258,6 +258,42 @@ int gstamd_audio_mixer_mix (int format, int channels, const GstAmdAudioMixerInpu
  * { kernel launches, inputs mixed, inputs skipped (mute / volume / empty), 0 }; returns 4 */
 int gstamd_audio_mixer_debug_launches (int32_t *out, int max_out);
 
+/* ---- volume (gst-plugins-base/gst/volume: gstvolume.c, gstvolumeorc.orc) --------------------------------------------------------------
+ * The element's sample loops on buffers that stay in device memory, many buffers a launch.  Two rules (DESIGN 3.10 has the tables):
+ * (a) gains == NULL - a fixed volume, as volume_update_volume picks the loop (gstvolume.c): the volume is held as a float; mute or 0.0
+ *     writes silence, (gint) (volume * 2048) == 2048 passes the bytes through, anything else runs volume_orc_process_int8 / _int16 /
+ *     _int32 (and their _clamp forms), volume_process_int24 (_clamp), volume_orc_scalarmultiply_f32_ns / _f64_ns (gstvolumeorc.orc);
+ * (b) gains != NULL - one double per frame, the value array a control binding fills, as volume_process_controlled_* applies it
+ *     (gstvolume.c): 1 and 2 channels through volume_orc_process_controlled_*_1ch / _2ch, every other count through the plain C loops,
+ *     which differ in rounding and in the denormal flush; mute turns every gain into +0.0 (volume_orc_prepare_volumes).
+ * Integer results saturate; ORC's denormal flush is done with bit operations; no fused multiply-add.  NaN payloads are not pinned.
+ * Formats: GSTAMD_AFMT_S8, _S16LE, _S24LE (3 bytes), _S32LE, _F32LE, _F64LE, interleaved - the six the element takes.  Every other
+ * GSTAMD_AFMT_* value returns GSTAMD_ERR_UNSUPPORTED. */
+typedef struct GstAmdAudioVolumeBuffer {
+  const void *in;        /* device pointer; aligned to the sample size (S24: any byte address) */
+  void *out;             /* == in: in place; else the two byte ranges must not overlap */
+  uint64_t frames;
+  double volume;         /* GstVolume "volume", 0 .. 10; ignored when gains != NULL */
+  const double *gains;   /* NULL: rule (a); else device pointer to `frames` doubles, 8-byte aligned: rule (b) */
+  int32_t mute, reserved;       /* GstVolume "mute" */
+} GstAmdAudioVolumeBuffer;
+
+/* volume_transform_ip on one buffer (gstvolume.c): gstamd_audio_volume_process_many with one entry */
+int gstamd_audio_volume_process (int format, int channels, const void *in, void *out, size_t frames,
+    double volume, int mute, const double *gains, void *stream);
+/* The same on n buffers of one format and channel count (gstvolume.c volume_transform_ip, gstvolumeorc.orc).  A buffer that passes through in
+ * place takes part in no launch; every other buffer - scaled, with gains, silenced, or passed through out of place as a copy - is one
+ * descriptor of a launch, in array order, 64 descriptors per launch, every further 64 one more launch on the same stream.  A buffer with
+ * frames == 0 does nothing.  Buffers of different entries must not overlap one another (not checked).  Asynchronous on `stream`.
+ * GSTAMD_ERR_INVALID, with nothing launched and no byte written: channels outside 1 .. 64, frames >= 2^30, in or out NULL with
+ * frames > 0, a misaligned pointer, in and out overlapping without being equal, a volume that is NaN, negative or above 10 (only when
+ * gains == NULL), n < 0 (or buffers == NULL with n > 0).  All buffers are checked before the first launch. */
+int gstamd_audio_volume_process_many (int format, int channels, const GstAmdAudioVolumeBuffer *buffers, int n, void *stream);
+/* what the calling thread's last gstamd_audio_volume_process / _process_many did (gstvolume.c has no counterpart; for tests):
+ * { kernel launches, buffers scaled (rule (a)'s formulas or rule (b)), buffers passed through, buffers silenced }; buffers without frames
+ * are in none of the three; returns 4 */
+int gstamd_audio_volume_debug_launches (int32_t *out, int max_out);
+
 #ifdef __cplusplus
 }
 #endif
